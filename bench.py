@@ -21,7 +21,13 @@ through the sharded path's collectives (sync set by block + all-gather,
 rank-ordered chain blocks with the state hand-over, gathered emission;
 strong scaling, max over ranks), checked against rank 0's one-GPU stream.
 
-Also reported:
+A plain run sets up, warms up, times ``--steps`` steps, writes the last step's outputs when
+``--dump-outputs DIR`` is given, and prints the result line.  ``--full`` adds every other leg:
+the CPU baseline, the PCIe-inclusive rate, the device decode check, the Huffman container, the
+N > 1 strong-scaling line, and the stream checks of ``--shard`` / ``--mode sss``; without it
+those fields of the line are null.
+
+Reported beside the headline value (cpu_baseline: ``--full`` only):
   roofline      the SSS kernel sequence (k_sss_stream pass 1 with the periodicity
                 filter, k_sss_runs on the stripes pass 1 stopped, the exact Q pass on
                 marked tiles and the re-run of stripes that see Q windows, the run-record
@@ -43,6 +49,8 @@ import sys
 import time
 from pathlib import Path
 
+import numpy as np
+
 ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT / "lz77-sss_amd"))
 
@@ -56,6 +64,50 @@ def make_text(lz, workload: str, n: int, rank: int):
     if workload == "genome":
         return lz.gen_genome(n, 64 << 20, 0.001, 7 + rank)
     raise SystemExit(f"unknown workload {workload}")
+
+
+DUMP_CAP_BYTES = 64 * 10**6  # --dump-outputs: the bytes of all files of one run together (MB = 10^6 B)
+DUMP_HEADER_BYTES = 1024     # reserved per file for the .npy header (128 bytes for these shapes)
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(dirpath, arrays: dict, cap_bytes: int | None = None) -> dict:
+    """--dump-outputs: writes each array (numpy, or a torch tensor on any device) as
+    DIR/<name>.npy in float64 (positions and lengths are integers below 2^53: exact).  The files
+    together, headers included, stay within cap_bytes (default DUMP_CAP_BYTES; a rank of N writes
+    within its N-th of it).  An array whose share is too small for all its rows is written as a
+    fixed sample of them: distinct row indices drawn once from a generator seeded with DUMP_SEED,
+    in ascending order, the same for every run of the same shape.  Returns {name: rows written}."""
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    cap = DUMP_CAP_BYTES if cap_bytes is None else cap_bytes
+    budget = max(cap // max(len(arrays), 1) - DUMP_HEADER_BYTES, 0)
+    written = {}
+    for name, a in arrays.items():
+        rows = int(a.shape[0])
+        per_row = 8
+        for k in tuple(a.shape[1:]):
+            per_row *= int(k)
+        keep = budget // per_row
+        if rows > keep:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=keep, replace=False))
+            if isinstance(a, np.ndarray):
+                a = a[idx]
+            else:
+                import torch
+
+                a = a.index_select(0, torch.from_numpy(idx).to(a.device))
+        if not isinstance(a, np.ndarray):
+            a = a.cpu().numpy()
+        path = d / f"{name}.npy"
+        np.save(path, np.ascontiguousarray(a, dtype=np.float64))
+        assert path.stat().st_size <= budget + DUMP_HEADER_BYTES, (name, path.stat().st_size)
+        written[name] = int(a.shape[0])
+    return written
+
+
+def dump_name(base: str, world: int, rank: int) -> str:
+    return base if world == 1 else f"{base}_rank{rank}"
 
 
 def aggregate(dt_local: float, n_per_rank: int, world: int, dist=None, device="cpu"):
@@ -197,11 +249,13 @@ def cpu_baseline_exact(lz, workload: str, sample_mib: int, transf_mode: str):
                                 "and the Pi / Psi scans"}
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--warmup", type=int, default=2,
+                    help="untimed steps before the timed ones; the default mode runs at least 1 (it sizes the "
+                         "pinned output buffer) and reports the number it ran")
     ap.add_argument("--workload", default="rr", choices=["rr", "genome", "chr19"],
                     help="chr19 (--shard only): configs[3]'s chr19-style text of --size-gib GiB generated in "
                          "HBM (59 MiB ACGT base block, 0.1%% mutations per copy), pos_t = uint64_t")
@@ -223,7 +277,17 @@ def main():
                     help="--mode approx: ONE text split across the ranks (sharded.factorize_sharded_resident: "
                          "sync set by block + all-gather, replicated phrases, rank-ordered greedy blocks, "
                          "rank-ordered emission; strong scaling) instead of one independent text per rank")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: CPU baseline, PCIe-inclusive rate, device "
+                         "decode check, Huffman container, the N > 1 strong-scaling line, the stream checks of "
+                         "--shard / --mode sss (a plain run leaves those fields null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(float64; at most 64 MB in all, a fixed seeded sample of rows beyond that): factors.npy "
+                         "= the (z, 2) {src, len} stream; --mode sss: sync_set.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -265,20 +329,25 @@ def main():
     t_load = time.perf_counter() - t_load0
 
     exact = args.mode == "exact"
+    # the first call sizes the pinned output buffer of the timed steps: at least one warmup step runs,
+    # and the line reports the number that ran
+    warmup = max(args.warmup, 1)
 
     # the factors reach the caller in host memory inside the timed step (the span
     # includes the output callback into a preallocated vector): a pinned buffer sized after warmup
     out_buf = [None]
+    copied = [False]
 
     def step():
         z = sess.factorize_exact(TRANSF[args.transf_mode], device=local_rank) if exact else \
             sess.factorize(device=local_rank, phr_mode=PHR[args.phr_mode])
-        if out_buf[0] is not None and z * 8 <= out_buf[0].numel():
+        copied[0] = out_buf[0] is not None and z * 8 <= out_buf[0].numel()
+        if copied[0]:
             sess.copy_factors(out_buf[0].data_ptr(), out_buf[0].numel())
         return z
 
     z_w = 0
-    for _ in range(max(args.warmup, 1)):
+    for _ in range(warmup):
         z_w = step()
     out_buf[0] = torch.empty(max(z_w * 8, 8) + (1 << 20), dtype=torch.uint8, pin_memory=True)
 
@@ -308,24 +377,40 @@ def main():
     # collectives (sync set by block + all-gather, rank-ordered chain blocks with the
     # state hand-over, gathered emission), timed the same way -- strong scaling beside the weak line
     strong = None
-    if world > 1 and not exact and args.phr_mode == "lpf_opt" and not os.environ.get("LZ77SSS_BENCH_NO_STRONG"):
+    if args.full and world > 1 and not exact and args.phr_mode == "lpf_opt" \
+            and not os.environ.get("LZ77SSS_BENCH_NO_STRONG"):
         try:
             strong = strong_scaling_line(args, lz, torch, dist, world, rank, local_rank, n, sess, int(z))
         except Exception as e:  # (reported in the line; the weak measurement above stands)
             strong = {"error": f"{type(e).__name__}: {e}"}
-    # PCIe-inclusive rate of one call (host text in, factors out), reported beside the HBM-resident value
-    t_out0 = time.perf_counter()
-    F = sess.factors(z)
-    t_out = time.perf_counter() - t_out0
-    del F
-    # device decode of the same factors, compared in HBM with the input (outside the timed region)
-    _, mism = sess.decode(out=False)
-    dec_ms = sess.phase_times().get("decode", float("nan"))
-    dec_rounds = sess.stats()[18]
-    # the Huffman factor container of the same factors (csrc/huffman.hip), host copy included
-    t_h0 = time.perf_counter()
-    hbytes = int(sess.huffman().size)
-    t_h = time.perf_counter() - t_h0
+    dumped = None
+    if args.dump_outputs:
+        # the caller's view of the last timed step: the pairs in the pinned host buffer
+        if copied[0]:
+            F = out_buf[0].numpy()[: z * 8].view(np.uint32).reshape(-1, 2)
+        else:  # (the buffer sized after warmup was too small: the same stream, read from the session)
+            F = sess.factors(z)
+        dumped = dump_outputs(args.dump_outputs, {dump_name("factors", world, rank): F}, DUMP_CAP_BYTES // world)
+        del F
+    pcie = decode_chk = huff = None
+    if args.full:
+        # PCIe-inclusive rate of one call (host text in, factors out), reported beside the HBM-resident value
+        t_out0 = time.perf_counter()
+        F = sess.factors(z)
+        t_out = time.perf_counter() - t_out0
+        del F
+        pcie = round(n / (dt + t_load + t_out) / 1e6, 2)
+        # device decode of the same factors, compared in HBM with the input (outside the timed region)
+        _, mism = sess.decode(out=False)
+        dec_ms = sess.phase_times().get("decode", float("nan"))
+        dec_rounds = sess.stats()[18]
+        decode_chk = {"mismatches": int(mism), "ms": round(dec_ms, 3), "jump_rounds": int(dec_rounds),
+                      "mbps": round(n / (dec_ms * 1e-3) / 1e6, 1)}
+        # the Huffman factor container of the same factors (csrc/huffman.hip), host copy included
+        t_h0 = time.perf_counter()
+        hbytes = int(sess.huffman().size)
+        t_h = time.perf_counter() - t_h0
+        huff = {"bytes": hbytes, "ms_incl_d2h": round(t_h * 1e3, 3)}
 
     if rank == 0:
         avg_ms = sum(kern_ms) / len(kern_ms)
@@ -339,7 +424,7 @@ def main():
             "unit": "MB/s",
             "n_gpus": world,
             "steps": args.steps,
-            "warmup": args.warmup,
+            "warmup": warmup,
             "ms_per_step": round(dt * 1e3, 3),
             "higher_is_better": True,
             "scaling": "weak",
@@ -362,10 +447,9 @@ def main():
                     "segments": int(st[16]), "completion_used": bool(st[19]),
                     "completion_start": int(st[20]), "windows": int(st[21])},
                 "phase_ms": {k: round(v, 3) for k, v in phases.items()},
-                "pcie_inclusive_mbps": round(n / (dt + t_load + t_out) / 1e6, 2),
-                "device_decode": {"mismatches": int(mism), "ms": round(dec_ms, 3), "jump_rounds": int(dec_rounds),
-                                  "mbps": round(n / (dec_ms * 1e-3) / 1e6, 1)},
-                "huffman_container": {"bytes": hbytes, "ms_incl_d2h": round(t_h * 1e3, 3)},
+                "pcie_inclusive_mbps": pcie,
+                "device_decode": decode_chk,
+                "huffman_container": huff,
                 "phase_mem_gib": {ph: {k: round(v / GIB, 3) for k, v in m.items()} for ph, m in pmem.items()},
             },
             "roofline": {
@@ -382,6 +466,8 @@ def main():
                 "avg_launch_ms": round(avg_ms, 4),
             },
             "cpu_baseline": None,
+            "full": bool(args.full),
+            "dumped_outputs": dumped,
         }
         if not exact and st and phases.get("sss"):
             # the whole SSS phase (Q anchors + run table + stream + compaction), same algorithmic bytes
@@ -399,7 +485,7 @@ def main():
                 "frac": round(n / (pipe * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "ms": round(pipe, 3)}
         if strong is not None:
             out["strong_scaling_one_text"] = strong
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             sample = args.cpu_sample_mib if args.cpu_sample_mib > 0 else args.size_mib
             if exact:
                 out["cpu_baseline"] = cpu_baseline_exact(lz, args.workload, sample, args.transf_mode)
@@ -515,7 +601,10 @@ def main_shard(args, lz, torch, dist, world, rank, local_rank):
     same = None
     st = sess.stats()
     verified = None
-    if rank == 0:
+    dumped = None
+    if args.dump_outputs and rank == 0:  # (every rank returns the same gathered stream)
+        dumped = dump_outputs(args.dump_outputs, {"factors": F})
+    if rank == 0 and args.full:
         # the one-GPU stream of the same text on the same session (round 3 took it from a fresh session
         # to dodge a fault whose cause, 2^32+ work-item launches past 2^26 sync positions, is fixed:
         # DESIGN.md 8), both streams checked against the text in HBM (lz77sss_session_verify)
@@ -555,9 +644,9 @@ def main_shard(args, lz, torch, dist, world, rank, local_rank):
                        "rank0_phase_mem_gib": {"note": "per phase: the session's device buffers when the phase was "
                                                        "enqueued (held) and their peak in it (peak), text excluded; "
                                                        "the GPU's free memory then (hbm_free)", **mem}},
-            "roofline": None, "cpu_baseline": None,
+            "roofline": None, "cpu_baseline": None, "full": bool(args.full), "dumped_outputs": dumped,
         }
-        if chr19 and world == 1 and not args.no_cpu_baseline:
+        if args.full and chr19 and world == 1 and not args.no_cpu_baseline:
             sess.close()  # (the host copy of the sample needs no device memory; free it anyway)
             sess = None
             out["cpu_baseline"] = cpu_baseline_chr19(lz, args.cpu_sample_mib << 20 if args.cpu_sample_mib > 0
@@ -617,7 +706,15 @@ def main_sss(args, lz, torch, dist, world, rank, local_rank):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     kms, kbytes = sess.sss_kernel_time()
-    if dist is not None and gathered[0] is not None:
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the step leaves its caller: the gathered set (N > 1), else this session's own (in HBM)
+        S = gathered[0] if dist is not None and gathered[0] is not None else sess.sync_set64(int(total))
+        dumped = dump_outputs(args.dump_outputs, {"sync_set": S})
+        del S
+    if not args.full:
+        ok = None
+    elif dist is not None and gathered[0] is not None:
         g = gathered[0]
         ok = bool(g.numel() < 2 or bool((g[1:] > g[:-1]).all().item()))
     else:
@@ -639,7 +736,7 @@ def main_sss(args, lz, torch, dist, world, rank, local_rank):
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                          "traffic": None, "algorithmic_bytes_per_launch": int(kbytes),
                          "avg_launch_ms": round(kms, 4)},
-            "cpu_baseline": None,
+            "cpu_baseline": None, "full": bool(args.full), "dumped_outputs": dumped,
         }
         print(json.dumps(out), flush=True)
     sess.close()

@@ -297,7 +297,7 @@ def test_gen_genome_pos_is_position_hashed(lz):
 
 @pytest.mark.parametrize("threads", [2, 4])
 def test_cpu_baseline_parallel_greedy_leg(orc, lz, threads):
-    """The CPU baseline's p > 1 leg (bench.py cpu_baseline): on a run-free genome-like text the
+    """The CPU baseline's p > 1 leg (bench.py --full, cpu_baseline): on a run-free genome-like text the
     reference selects its racy parallel greedy (lz77_sss.hpp:467-474, greedy_parallel.cpp:31-285);
     the restated leg must take that path and still emit a valid stream (decode == T).  Timing
     only: its stream depends on the thread interleaving and is no parity target."""

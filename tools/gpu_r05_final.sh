@@ -10,16 +10,16 @@ if [ "$1" = tests ]; then
     tail -3 "$OUT/pytest_gpu.log"
     exit 0
 fi
-timeout -k 10 300 python -u bench.py > "$OUT/bench_rr.json" 2> "$OUT/bench_rr.err" || exit 1
-timeout -k 10 300 python -u bench.py --mode exact --workload genome --steps 2 --warmup 1 \
+timeout -k 10 300 python -u bench.py --full > "$OUT/bench_rr.json" 2> "$OUT/bench_rr.err" || exit 1
+timeout -k 10 300 python -u bench.py --full --mode exact --workload genome --steps 2 --warmup 1 \
     > "$OUT/bench_genome_exact.json" 2> "$OUT/bench_genome_exact.err" || exit 1
-timeout -k 10 300 python -u bench.py --mode exact --workload rr --steps 3 --warmup 1 \
+timeout -k 10 300 python -u bench.py --full --mode exact --workload rr --steps 3 --warmup 1 \
     > "$OUT/bench_rr_exact.json" 2> "$OUT/bench_rr_exact.err" || exit 1
 cat "$OUT"/bench_*.json | cut -c1-400
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 240 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/prof_rr" -o run -- \
-    python3 "$REPO/bench.py" --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/prof_rr.json" 2> "$OUT/prof_rr.err" || exit 1
+    python3 "$REPO/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/prof_rr.json" 2> "$OUT/prof_rr.err" || exit 1
 timeout -k 10 240 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/prof_genome_exact" -o run -- \
-    python3 "$REPO/bench.py" --mode exact --workload genome --steps 2 --warmup 1 --no-cpu-baseline \
+    python3 "$REPO/bench.py" --full --mode exact --workload genome --steps 2 --warmup 1 --no-cpu-baseline \
     > "$OUT/prof_genome_exact.json" 2> "$OUT/prof_genome_exact.err" || exit 1
 echo "r05 final bench done"
