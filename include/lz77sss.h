@@ -143,6 +143,35 @@ int lz77sss_decode_u32(const lz77sss_factor32* factors, uint64_t nf, uint8_t* ou
 int lz77sss_decode_u32_device(const lz77sss_factor32* factors, uint64_t nf, uint8_t* out, uint64_t n, int device);
 int lz77sss_decode_u64(const lz77sss_factor64* factors, uint64_t nf, uint8_t* out, uint64_t n);
 int lz77sss_decode_u64_device(const lz77sss_factor64* factors, uint64_t nf, uint8_t* out, uint64_t n, int device);
+/* Decode on `device` in bounded device memory (csrc/decode_win.hip): the stream is validated
+ * over its factors (the lengths sum to n, every copy has src < start; LZ77SSS_EINVAL before any
+ * output is written), then decoded left to right in windows of `window` positions (rounded up
+ * to a multiple of 4096, at most 2^31; 0 = chosen by the library).  Device memory: the n output
+ * bytes, 8 B per window position and 8 B per factor -- where the whole-text decode above needs
+ * 16 B (u32) or 24 B (u64) per position of the text. */
+int lz77sss_decode_u32_device_windowed(const lz77sss_factor32* factors, uint64_t nf, uint8_t* out, uint64_t n,
+                                       uint64_t window, int device);
+int lz77sss_decode_u64_device_windowed(const lz77sss_factor64* factors, uint64_t nf, uint8_t* out, uint64_t n,
+                                       uint64_t window, int device);
+/* Bytes [pos, pos + len) of the text of length n that the factors encode, without decoding
+ * [0, pos): every output position walks its chain of copy sources down to a literal.  A stream
+ * is validated as above; pos + len > n is LZ77SSS_EINVAL; len == 0 succeeds and writes nothing.
+ * A position whose chain is longer than the hop budget (environment LZ77SSS_EXTRACT_MAX_HOPS,
+ * read per call; default 4096) makes the call answer from a windowed decode of [0, pos + len)
+ * instead, so the cost is bounded for every valid stream; a range of 2^24 bytes or more with
+ * pos <= len is answered that way at once (it is cheaper).  info (may be NULL) receives
+ * [the path that ran, the largest hop count of the walk]. */
+enum { LZ77SSS_EXTRACT_NONE = 0 /* len == 0 */, LZ77SSS_EXTRACT_WALK = 1, LZ77SSS_EXTRACT_PREFIX_DECODE = 2 };
+int lz77sss_extract_u32_device(const lz77sss_factor32* factors, uint64_t nf, uint64_t n, uint64_t pos, uint64_t len,
+                               uint8_t* out, int device, uint64_t* info);
+int lz77sss_extract_u64_device(const lz77sss_factor64* factors, uint64_t nf, uint64_t n, uint64_t pos, uint64_t len,
+                               uint8_t* out, int device, uint64_t* info);
+/* The same on the host, beside lz77sss_decode_u32 / _u64: a per-position walk over a prefix sum
+ * of the lengths (which must sum to n). */
+int lz77sss_extract_u32(const lz77sss_factor32* factors, uint64_t nf, uint64_t n, uint64_t pos, uint64_t len,
+                        uint8_t* out);
+int lz77sss_extract_u64(const lz77sss_factor64* factors, uint64_t nf, uint64_t n, uint64_t pos, uint64_t len,
+                        uint8_t* out);
 /* The reference's pos_t = uint64_t factor stream (lz77_sss.hpp:149-173): 5 bytes src, 5
  * bytes len, little endian; out holds 10 * nf bytes.  Returns LZ77SSS_EINVAL if a value
  * needs more than 40 bits. */
@@ -177,6 +206,17 @@ int lz77sss_session_get_factors64(lz77sss_session* s, lz77sss_factor64* out, uin
  * positions where the decoded text differs from the loaded one (0 = round trip
  * holds), without leaving HBM.  Timed as phase "decode". */
 int lz77sss_session_decode(lz77sss_session* s, uint8_t* out, uint64_t cap, uint64_t* mismatches);
+/* The same in bounded device memory (lz77sss_decode_u32_device_windowed): window in positions,
+ * 0 = chosen by the library.  Any session kind; a text of any size whose n output bytes fit
+ * beside it.  Timed as phase "decode".  Fails with LZ77SSS_EINVAL when the session holds no
+ * factorization and after a skip_phrases call, as lz77sss_session_verify does. */
+int lz77sss_session_decode_windowed(lz77sss_session* s, uint64_t window, uint8_t* out, uint64_t cap,
+                                    uint64_t* mismatches);
+/* Bytes [pos, pos + len) of the last factorization's text into out (host; see
+ * lz77sss_extract_u32_device); mismatches (may be NULL) receives the number of those positions
+ * that differ from the loaded text.  Timed as phase "extract"; stats 29 and 30 report the path
+ * that ran (LZ77SSS_EXTRACT_*) and the largest hop count.  Fails as decode_windowed does. */
+int lz77sss_session_extract(lz77sss_session* s, uint64_t pos, uint64_t len, uint8_t* out, uint64_t* mismatches);
 /* Checks the factors of the last factorization against the loaded text without decoding
  * them (a 50 GiB stream needs no n-sized decode buffers): *bad_positions = the number of
  * positions whose factor does not reproduce the text (a literal with another byte, a copy
@@ -247,7 +287,8 @@ int lz77sss_session_phase_mem(lz77sss_session* s, uint64_t* held, uint64_t* peak
 /* Statistics of the last factorize call: [size_sss, has_runs, num_lpf, len_lpf_phr,
  * num_gaps, patt_lens[5], roll_threshold, log2_size_h, greedy_rounds, fixups, ...]; after an
  * exact-smpl call 24..28 = samples, delta, phrase tasks, chunks << 32 | doubling levels, and 1 when
- * the sources follow the reference's visit order. */
+ * the sources follow the reference's visit order; after lz77sss_session_extract
+ * 29 = the path that ran (LZ77SSS_EXTRACT_*), 30 = the largest hop count of its walk. */
 int lz77sss_session_stats(lz77sss_session* s, uint64_t* out, int cap);
 void lz77sss_session_destroy(lz77sss_session* s);
 

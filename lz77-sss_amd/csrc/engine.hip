@@ -8,6 +8,7 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <memory>
@@ -400,6 +401,13 @@ struct engine64_impl final : lz::engine_if {
         LZ_HIP(hipStreamSynchronize(E.st));
         return bad;
     }
+    void check_verifiable() const override { E.check_verifiable(); }
+    u64 decode_windowed(const u64* F, u64 nf, u64 n_out, u64 window, u8* d_out, bool cmp) override {
+        return E.decode_windowed(F, nf, n_out, window, d_out, cmp ? E.d_text : nullptr);
+    }
+    const u8* extract(const u64* F, u64 nf, u64 n_tot, u64 pos, u64 len, bool cmp, u64* mism, u64* info) override {
+        return E.extract_device(F, nf, n_tot, pos, len, cmp ? E.d_text : nullptr, mism, info);
+    }
     void sss(u64* size, int* has_runs) override {
         LZ_HIP(hipSetDevice(E.device));
         E.build_sss(E.d_text);
@@ -672,6 +680,69 @@ LZ77SSS_API int lz77sss_session_verify(lz77sss_session* s, uint64_t* bad_positio
         LZ_HIP(hipSetDevice(E.device));
         *bad_positions = E.verify_factors(E.fact.p, E.num_fact, E.n, E.d_text, first_bad);
         LZ_HIP(hipStreamSynchronize(E.st));
+    });
+}
+
+// the decode in bounded memory (csrc/decode_win.hip): the factors of the last factorization
+LZ77SSS_API int lz77sss_session_decode_windowed(lz77sss_session* s, uint64_t window, uint8_t* out, uint64_t cap,
+                                                uint64_t* mismatches) {
+    if (!s) return LZ77SSS_EINVAL;
+    return guarded([&] {
+        if (s->E64) {
+            lz::engine_if& E = *s->E64;
+            E.check_verifiable();
+            if (out && cap < E.n()) throw lz::error(LZ77SSS_EINVAL, "output capacity too small");
+            LZ_HIP(hipSetDevice(E.device()));
+            lz::u8* d_out = E.n() ? E.dec_out(E.n()) : nullptr;
+            E.timer().begin(E.stream());
+            const uint64_t bad = E.decode_windowed(E.factors(), E.num_fact(), E.n(), window, d_out, mismatches != nullptr);
+            E.timer().mark("decode");
+            if (E.stats().size() > 18) E.stats()[18] = E.dec_rounds();
+            if (mismatches) *mismatches = bad;
+            if (out && d_out) LZ_HIP(hipMemcpyAsync(out, d_out, E.n(), hipMemcpyDeviceToHost, E.stream()));
+            LZ_HIP(hipStreamSynchronize(E.stream()));
+            return;
+        }
+        lz::engine& E = s->E;
+        E.check_verifiable();
+        if (out && cap < E.n) throw lz::error(LZ77SSS_EINVAL, "output capacity too small");
+        LZ_HIP(hipSetDevice(E.device));
+        lz::u8* d_out = E.n ? E.dec_out.get(E.n) : nullptr;
+        E.timer.begin(E.st);
+        const uint64_t bad = E.decode_windowed(E.fact.p, E.num_fact, E.n, window, d_out, mismatches ? E.d_text : nullptr);
+        E.timer.mark("decode");
+        if (E.stats.size() > 18) E.stats[18] = E.dec_rounds;
+        if (mismatches) *mismatches = bad;
+        if (out && d_out) LZ_HIP(hipMemcpyAsync(out, d_out, E.n, hipMemcpyDeviceToHost, E.st));
+        LZ_HIP(hipStreamSynchronize(E.st));
+    });
+}
+
+// bytes [pos, pos + len) of the last factorization's text (csrc/decode_win.hip extract_device)
+LZ77SSS_API int lz77sss_session_extract(lz77sss_session* s, uint64_t pos, uint64_t len, uint8_t* out,
+                                        uint64_t* mismatches) {
+    if (!s || (!out && len)) return LZ77SSS_EINVAL;
+    return guarded([&] {
+        const uint64_t n = s->E64 ? s->E64->n() : s->E.n;
+        if (s->E64) s->E64->check_verifiable();
+        else s->E.check_verifiable();
+        if (pos > n || len > n - pos) throw lz::error(LZ77SSS_EINVAL, "range past the end of the text");
+        hipStream_t st = s->E64 ? s->E64->stream() : s->E.st;
+        lz::phase_timer& timer = s->E64 ? s->E64->timer() : s->E.timer;
+        std::vector<uint64_t>& stats = s->E64 ? s->E64->stats() : s->E.stats;
+        LZ_HIP(hipSetDevice(s->E64 ? s->E64->device() : s->E.device));
+        uint64_t info[2] = {0, 0};
+        timer.begin(st);
+        const lz::u8* d = s->E64 ? s->E64->extract(s->E64->factors(), s->E64->num_fact(), n, pos, len,
+                                                   mismatches != nullptr, mismatches, info)
+                                 : s->E.extract_device(s->E.fact.p, s->E.num_fact, n, pos, len,
+                                                       mismatches ? s->E.d_text : nullptr, mismatches, info);
+        timer.mark("extract");
+        if (stats.size() < 31) stats.resize(31, 0);
+        stats[29] = info[0];
+        stats[30] = info[1];
+        if (d && len) LZ_HIP(hipMemcpyAsync(out, d, len, hipMemcpyDeviceToHost, st));
+        LZ_HIP(hipStreamSynchronize(st));
     });
 }
 
@@ -1154,6 +1225,131 @@ LZ77SSS_API int lz77sss_decode_u64_device(const lz77sss_factor64* f, uint64_t nf
     return rc;
 }
 
+}  // extern "C"
+
+// one-shot forms of the bounded-memory decode and the range extract (csrc/decode_win.hip): the
+// factors go up, the bytes come down; the session holds no text.  Argument errors are reported
+// before the device is touched.  extract: bytes [pos, pos + len); else the whole text in windows
+template <class FACT>
+static int one_shot_decode_win(const FACT* f, uint64_t nf, uint64_t n, uint64_t window, bool extract, uint64_t pos,
+                               uint64_t len, uint8_t* out, int device, uint64_t* info) {
+    constexpr bool wide = sizeof(FACT) == 16;
+    const uint64_t nout = extract ? len : n;
+    int rc = guarded([&] {
+        if ((!f && nf) || (!out && nout)) throw lz::error(LZ77SSS_EINVAL, "NULL argument");
+        if (extract && (pos > n || len > n - pos)) throw lz::error(LZ77SSS_EINVAL, "range past the end of the text");
+        if (n == 0 && nf) throw lz::error(LZ77SSS_EINVAL, "factors for an empty text");
+        if (n && (nf == 0 || nf > n)) throw lz::error(LZ77SSS_EINVAL, "factor count does not fit the text length");
+    });
+    if (info) info[0] = LZ77SSS_EXTRACT_NONE, info[1] = 0;
+    if (rc || nout == 0) return rc;
+    lz77sss_session* s = nullptr;
+    rc = wide ? lz77sss_session_create64(device, 0, &s) : lz77sss_session_create(device, 0, &s);
+    if (rc) return rc;
+    rc = guarded([&] {
+        uint64_t inf[2] = {0, 0};
+        const lz::u8* d = nullptr;
+        hipStream_t st;
+        if constexpr (wide) {
+            lz::engine_if& E = *s->E64;
+            st = E.stream();
+            lz::u64* F = E.factors_buf(nf);
+            LZ_HIP(hipMemcpyAsync(F, f, nf * sizeof(FACT), hipMemcpyHostToDevice, st));
+            if (extract) {
+                d = E.extract(F, nf, n, pos, len, false, nullptr, inf);
+            } else {
+                lz::u8* d_out = E.dec_out(n);
+                E.decode_windowed(F, nf, n, window, d_out, false);
+                d = d_out;
+            }
+        } else {
+            lz::engine& E = s->E;
+            st = E.st;
+            lz::u32* F = E.fact.get(2 * nf + 2);
+            LZ_HIP(hipMemcpyAsync(F, f, nf * sizeof(FACT), hipMemcpyHostToDevice, st));
+            if (extract) {
+                d = E.extract_device(F, nf, n, pos, len, nullptr, nullptr, inf);
+            } else {
+                lz::u8* d_out = E.dec_out.get(n);
+                E.decode_windowed(F, nf, n, window, d_out, nullptr);
+                d = d_out;
+            }
+        }
+        if (info) info[0] = inf[0], info[1] = inf[1];
+        LZ_HIP(hipMemcpyAsync(out, d, nout, hipMemcpyDeviceToHost, st));
+        LZ_HIP(hipStreamSynchronize(st));
+    });
+    lz77sss_session_destroy(s);
+    return rc;
+}
+
+// range extract on the host: a per-position walk over the prefix sum of the lengths.  A hop
+// that lands inside the part of the range already written takes its byte from there
+template <class FACT>
+static int host_extract(const FACT* f, uint64_t nf, uint64_t n, uint64_t pos, uint64_t len, uint8_t* out) {
+    return guarded([&] {
+        if ((!f && nf) || (!out && len)) throw lz::error(LZ77SSS_EINVAL, "NULL argument");
+        if (pos > n || len > n - pos) throw lz::error(LZ77SSS_EINVAL, "range past the end of the text");
+        if (nf > n) throw lz::error(LZ77SSS_EINVAL, "factor count does not fit the text length");
+        std::vector<uint64_t> start(nf + 1);
+        uint64_t at = 0;
+        for (uint64_t k = 0; k < nf; k++) {
+            start[k] = at;
+            const uint64_t l = f[k].len ? (uint64_t)f[k].len : 1;
+            if (at >= n || l > n - at) throw lz::error(LZ77SSS_EINVAL, "factor lengths do not sum to n");
+            if (f[k].len && (uint64_t)f[k].src >= at) throw lz::error(LZ77SSS_EINVAL, "factor source not before its position");
+            at += l;
+        }
+        start[nf] = at;
+        if (at != n) throw lz::error(LZ77SSS_EINVAL, "factor lengths do not sum to n");
+        uint64_t k = 0;  // the factor of the last position looked up (neighbours share it)
+        for (uint64_t i = 0; i < len; i++) {
+            uint64_t p = pos + i;
+            for (;;) {
+                if (p >= pos && p < pos + i) {
+                    out[i] = out[p - pos];
+                    break;
+                }
+                if (p < start[k] || p >= start[k + 1])
+                    k = (uint64_t)(std::upper_bound(start.begin(), start.end() - 1, p) - start.begin()) - 1;
+                if (f[k].len == 0) {
+                    out[i] = (uint8_t)f[k].src;
+                    break;
+                }
+                const uint64_t d = start[k] - f[k].src;
+                uint64_t off = p - start[k];
+                if (off >= d) off %= d;
+                p = f[k].src + off;
+            }
+        }
+    });
+}
+
+extern "C" {
+LZ77SSS_API int lz77sss_decode_u32_device_windowed(const lz77sss_factor32* f, uint64_t nf, uint8_t* out, uint64_t n,
+                                                   uint64_t window, int device) {
+    return one_shot_decode_win(f, nf, n, window, false, 0, 0, out, device, nullptr);
+}
+LZ77SSS_API int lz77sss_decode_u64_device_windowed(const lz77sss_factor64* f, uint64_t nf, uint8_t* out, uint64_t n,
+                                                   uint64_t window, int device) {
+    return one_shot_decode_win(f, nf, n, window, false, 0, 0, out, device, nullptr);
+}
+LZ77SSS_API int lz77sss_extract_u32_device(const lz77sss_factor32* f, uint64_t nf, uint64_t n, uint64_t pos,
+                                           uint64_t len, uint8_t* out, int device, uint64_t* info) {
+    return one_shot_decode_win(f, nf, n, 0, true, pos, len, out, device, info);
+}
+LZ77SSS_API int lz77sss_extract_u64_device(const lz77sss_factor64* f, uint64_t nf, uint64_t n, uint64_t pos,
+                                           uint64_t len, uint8_t* out, int device, uint64_t* info) {
+    return one_shot_decode_win(f, nf, n, 0, true, pos, len, out, device, info);
+}
+LZ77SSS_API int lz77sss_extract_u32(const lz77sss_factor32* f, uint64_t nf, uint64_t n, uint64_t pos, uint64_t len,
+                                    uint8_t* out) {
+    return host_extract(f, nf, n, pos, len, out);
+}
+LZ77SSS_API int lz77sss_extract_u64(const lz77sss_factor64* f, uint64_t nf, uint64_t n, uint64_t pos, uint64_t len,
+                                    uint8_t* out) {
+    return host_extract(f, nf, n, pos, len, out);
+}
 }  // extern "C"
 // decode: algorithms/common.cpp:31-54 (sequential; forward byte copy allows overlap)
 template <class FACT>

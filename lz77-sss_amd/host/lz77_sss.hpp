@@ -189,4 +189,21 @@ class lz77_sss {
         else check(lz77sss_decode_u32(fs.data(), fs.size(), buf.data(), output_size));
         for (uint64_t i = 0; i < output_size; i++) *out_it++ = static_cast<char>(buf[i]);
     }
+
+    // bytes [pos, pos + len) of the text of output_size bytes the factors encode, without
+    // decoding the text before them (no reference counterpart; lz77sss_extract_u32 / _u64)
+    template <typename fact_it_t, typename out_it_t>
+    static void extract(fact_it_t fact_it, out_it_t out_it, pos_t output_size, pos_t pos, pos_t len) {
+        std::vector<uint8_t> buf(len);
+        std::vector<cfactor> fs;
+        for (uint64_t at = 0; at < output_size;) {
+            const factor f = *fact_it;
+            ++fact_it;
+            fs.push_back({f.src, f.len});
+            at += f.length();
+        }
+        if constexpr (wide) check(lz77sss_extract_u64(fs.data(), fs.size(), output_size, pos, len, buf.data()));
+        else check(lz77sss_extract_u32(fs.data(), fs.size(), output_size, pos, len, buf.data()));
+        for (uint64_t i = 0; i < len; i++) *out_it++ = static_cast<char>(buf[i]);
+    }
 };

@@ -234,6 +234,16 @@ struct engine {
     dbuf<u64> dec_len64, dec_start64;
     dbuf<u8> dec_out;
     u32 dec_rounds = 0;
+    // windowed decode / range extract (csrc/decode_win.hip): window-relative references, the
+    // extracted bytes; the defaults are the measured ones of DESIGN.md 4.8
+    static constexpr u64 DW_DEFAULT_WINDOW = 1ull << 26;
+    static constexpr u64 DW_DEFAULT_MAX_HOPS = 4096;
+    // an extract of len >= DW_DIRECT_MIN_LEN bytes with pos + len <= DW_DIRECT_RATIO * len decodes the prefix
+    static constexpr u64 DW_DIRECT_MIN_LEN = 1ull << 24, DW_DIRECT_RATIO = 2;
+    dbuf<u32> dw_ref, dw_ref2;
+    dbuf<u8> dw_ext;
+    dbuf<u64> dw_idx;  // extract: the factor covering every 4096th position (8 B per 4096 text bytes)
+    u64 dw_windows = 0;
     u64 num_fact = 0;
     int last_fact_mode = -1;  // fact_mode of the last factorize call (-1: none yet)
     // lz77sss_session_verify checks the factors in HBM against the text in HBM: a factorization must
@@ -300,6 +310,12 @@ struct engine {
     void build_adjacent(smpl_view& V);                                                                 // csrc/smpl.hip
     u64 decode_device(const pos_t* F, u64 nf, u64 n_out, u8* out, const u8* cmp);
     u64 verify_factors(const pos_t* F, u64 nf, u64 n_out, const u8* T, u64* first_bad = nullptr);  // csrc/decode.hip
+    // csrc/decode_win.hip
+    u64 decode_windowed(const pos_t* F, u64 nf, u64 n_out, u64 window, u8* out, const u8* cmp);
+    const u8* extract_device(const pos_t* F, u64 nf, u64 n_tot, u64 pos, u64 len, const u8* cmp, u64* mism, u64* info);
+    const u64* dw_starts(const pos_t* F, u64 nf, u64 n_out);
+    u64 dw_window(u64 window, u64 n_dec) const;
+    u64 dw_run(const pos_t* F, u64 nf, const u64* start, u64 n_dec, u64 W, u8* out, const u8* cmp);
     void debug_verify_phrases(const char* what);  // LZ77SSS_DEBUG_VERIFY (csrc/decode.hip)
     void debug_verify_lce(const char* what);
     lce_view view(const u8* T) const;

@@ -25,6 +25,12 @@ struct engine_if {
     virtual u64 decode(const u64* F, u64 nf, u64 n_out, u8* d_out, bool cmp_with_text) = 0;
     virtual u8* dec_out(u64 n) = 0;
     virtual u64 verify(u64* first_bad) = 0;  // the factors against the loaded text (csrc/decode.hip)
+    // csrc/decode_win.hip: the windowed decode, and bytes [pos, pos + len) of the text (device
+    // bytes; info = path, largest hop count); check_verifiable as lz77sss_session_verify
+    virtual void check_verifiable() const = 0;
+    virtual u64 decode_windowed(const u64* F, u64 nf, u64 n_out, u64 window, u8* d_out, bool cmp_with_text) = 0;
+    virtual const u8* extract(const u64* F, u64 nf, u64 n_tot, u64 pos, u64 len, bool cmp_with_text, u64* mism,
+                              u64* info) = 0;
     virtual void sss(u64* size, int* has_runs) = 0;
     virtual u64 sss_size() const = 0;
     virtual const u64* sss_ptr() const = 0;

@@ -6,6 +6,9 @@ of LukasNalbach/lz77-sss; ``pos64=True`` selects uint64_t, which texts past 2^32
 * ``factorize_approximate(text, fact_mode=GREEDY, phr_mode=LPF_OPT, ...)``
   <- ``lz77_sss<>::factorize_approximate<fact_mode, phr_mode, tau>`` (:176-186)
 * ``decode(factors, n)`` <- ``lz77_sss<>::decode`` (:202-203, algorithms/common.cpp:31-54)
+* ``decode_device_windowed(factors, n, window)`` / ``extract_device(factors, n, pos, length)`` /
+  ``extract(factors, n, pos, length)``: no reference counterpart -- the decode in bounded device
+  memory and a byte range of the text without the text before it (csrc/decode_win.hip)
 * factors are an ``(z, 2)`` uint32 (uint64 for pos64) array of ``(src, len)`` =
   ``lz77_sss<>::factor`` (:129-147); a literal has ``len == 0`` and ``src`` = the byte.
 
@@ -26,6 +29,7 @@ NAIVE, WITH_SAMPLES, WITHOUT_SAMPLES = 0, 1, 2               # enum transform_mo
 FULL_SA = 3                                                    # device extension: LPF over the full suffix array
 DEFAULT_TAU = 512
 OK, EINVAL, ENODEV, EHIP, ENOMEM, ECALLBACK, EINTERNAL = 0, -1, -2, -3, -4, -5, -6  # include/lz77sss.h
+EXTRACT_NONE, EXTRACT_WALK, EXTRACT_PREFIX_DECODE = 0, 1, 2                       # the path an extract took
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("LZ77SSS_LIB", _HERE / "lib" / "liblz77sss_hip.so"))
@@ -71,6 +75,14 @@ _SYMBOLS = {
     "lz77sss_decode_u32": (ctypes.c_int, [_P, _U64, _P, _U64]),
     "lz77sss_decode_u32_device": (ctypes.c_int, [_P, _U64, _P, _U64, ctypes.c_int]),
     "lz77sss_session_decode": (ctypes.c_int, [_P, _P, _U64, ctypes.POINTER(_U64)]),
+    "lz77sss_session_decode_windowed": (ctypes.c_int, [_P, _U64, _P, _U64, ctypes.POINTER(_U64)]),
+    "lz77sss_session_extract": (ctypes.c_int, [_P, _U64, _U64, _P, ctypes.POINTER(_U64)]),
+    "lz77sss_decode_u32_device_windowed": (ctypes.c_int, [_P, _U64, _P, _U64, _U64, ctypes.c_int]),
+    "lz77sss_decode_u64_device_windowed": (ctypes.c_int, [_P, _U64, _P, _U64, _U64, ctypes.c_int]),
+    "lz77sss_extract_u32_device": (ctypes.c_int, [_P, _U64, _U64, _U64, _U64, _P, ctypes.c_int, _P]),
+    "lz77sss_extract_u64_device": (ctypes.c_int, [_P, _U64, _U64, _U64, _U64, _P, ctypes.c_int, _P]),
+    "lz77sss_extract_u32": (ctypes.c_int, [_P, _U64, _U64, _U64, _U64, _P]),
+    "lz77sss_extract_u64": (ctypes.c_int, [_P, _U64, _U64, _U64, _U64, _P]),
     "lz77sss_session_verify": (ctypes.c_int, [_P, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "lz77sss_session_create": (ctypes.c_int, [ctypes.c_int, _U64, ctypes.POINTER(_P)]),
     "lz77sss_session_load": (ctypes.c_int, [_P, _P, _U64]),
@@ -280,6 +292,33 @@ class Session:
                                                      self.n if out else 0, ctypes.byref(m) if verify else None))
         return (buf[:self.n] if out else None), (m.value if verify else None)
 
+    def decode_windowed(self, window: int = 0, out: bool = True, verify: bool = True):
+        """Decodes the last factorization on the device in bounded memory (csrc/decode_win.hip):
+        windows of `window` positions (0: chosen by the library), 8 B of scratch per window position
+        whatever n is.  Returns (text or None, mismatches vs the loaded text or None)."""
+        buf = np.empty(max(self.n, 1), np.uint8) if out else None
+        m = _U64()
+        _check(load_library().lz77sss_session_decode_windowed(
+            self._h, window, buf.ctypes.data_as(_P) if out else None, self.n if out else 0,
+            ctypes.byref(m) if verify else None))
+        return (buf[:self.n] if out else None), (m.value if verify else None)
+
+    def extract(self, pos: int, length: int, verify: bool = False):
+        """Bytes [pos, pos + length) of the last factorization's text, without decoding the text
+        before them (csrc/decode_win.hip).  With verify=True: (bytes, mismatches vs the loaded
+        text).  extract_info() tells which path answered."""
+        buf = np.empty(max(min(length, self.n), 1), np.uint8)  # (a longer range is rejected by the library)
+        m = _U64()
+        _check(load_library().lz77sss_session_extract(self._h, pos, length, buf.ctypes.data_as(_P),
+                                                      ctypes.byref(m) if verify else None))
+        return (buf[:length], m.value) if verify else buf[:length]
+
+    def extract_info(self):
+        """(path, largest hop count) of the last extract: EXTRACT_WALK or EXTRACT_PREFIX_DECODE
+        (a chain passed the hop budget LZ77SSS_EXTRACT_MAX_HOPS); EXTRACT_NONE for an empty range."""
+        st = self.stats()
+        return (st[29], st[30]) if len(st) > 30 else (EXTRACT_NONE, 0)
+
     def verify(self, first: bool = False):
         """Positions of the loaded text that the last factorization does not reproduce, checked in
         HBM without decoding (lz77sss_session_verify; 0 <=> decode(F) == T; any size).  With
@@ -454,6 +493,43 @@ def decode_device(factors: np.ndarray, n: int, device: int = 0) -> np.ndarray:
     fn = load_library().lz77sss_decode_u64_device if wide else load_library().lz77sss_decode_u32_device
     _check(fn(f.ctypes.data_as(_P), f.shape[0], out.ctypes.data_as(_P), n, device))
     return out[:n]
+
+
+def _factor_array(factors):
+    wide = np.asarray(factors).dtype == np.uint64
+    return wide, np.ascontiguousarray(factors, dtype=np.uint64 if wide else np.uint32).reshape(-1, 2)
+
+
+def decode_device_windowed(factors: np.ndarray, n: int, window: int = 0, device: int = 0) -> np.ndarray:
+    """decode_device in bounded device memory (csrc/decode_win.hip): windows of `window` positions
+    (rounded up to a multiple of 4096; 0: chosen by the library)."""
+    wide, f = _factor_array(factors)
+    out = np.empty(max(n, 1), np.uint8)
+    lib = load_library()
+    fn = lib.lz77sss_decode_u64_device_windowed if wide else lib.lz77sss_decode_u32_device_windowed
+    _check(fn(f.ctypes.data_as(_P), f.shape[0], out.ctypes.data_as(_P), n, window, device))
+    return out[:n]
+
+
+def extract_device(factors: np.ndarray, n: int, pos: int, length: int, device: int = 0, info: bool = False):
+    """Bytes [pos, pos + length) of the text of length n the factors encode, on the device, without
+    decoding [0, pos).  With info=True: (bytes, (path, largest hop count))."""
+    wide, f = _factor_array(factors)
+    out = np.empty(max(min(length, n), 1), np.uint8)  # (a longer range is rejected by the library)
+    inf = (_U64 * 2)()
+    lib = load_library()
+    fn = lib.lz77sss_extract_u64_device if wide else lib.lz77sss_extract_u32_device
+    _check(fn(f.ctypes.data_as(_P), f.shape[0], n, pos, length, out.ctypes.data_as(_P), device, inf))
+    return (out[:length], (int(inf[0]), int(inf[1]))) if info else out[:length]
+
+
+def extract(factors: np.ndarray, n: int, pos: int, length: int) -> np.ndarray:
+    """The same on the host (a per-position walk over the prefix sum of the lengths)."""
+    wide, f = _factor_array(factors)
+    out = np.empty(max(min(length, n), 1), np.uint8)  # (a longer range is rejected by the library)
+    fn = load_library().lz77sss_extract_u64 if wide else load_library().lz77sss_extract_u32
+    _check(fn(f.ctypes.data_as(_P), f.shape[0], n, pos, length, out.ctypes.data_as(_P)))
+    return out[:length]
 
 
 def serialize_factors64(factors: np.ndarray) -> bytes:
