@@ -14,6 +14,13 @@
 #include <utility>
 #include <vector>
 
+namespace lz {
+// counters of the last call (lz77sss_session_stats).  A factorization starts from STATS_N zeroed
+// entries; a decode writes its rounds into one of them, an extract appends its path and largest
+// hop count (slot STATS_N itself belongs to exact-smpl, csrc/smpl.hip)
+constexpr size_t STATS_N = 28, STAT_DEC_ROUNDS = 18, STAT_EXTRACT = STATS_N + 1;
+}  // namespace lz
+
 namespace LZ_NS {
 
 struct lpf3 { pos_t beg, end, src; };
@@ -258,6 +265,7 @@ struct engine {
     dbuf<u8> hf_tabs, hf_words, hf_out;  // Huffman factor container (csrc/huffman.hip)
     u64 ssz_size = 0;
     std::vector<u64> stats;
+    void reset_stats() { stats.assign(STATS_N, 0); }
 
     phase_timer timer;
 
@@ -281,7 +289,7 @@ struct engine {
     void build_sss(const u8* T);
     bool build_q_runs(const u8* T);     // Q anchors + periodic-run table only
     void run_chains(u64 nanch, const u32* tiles, u64 m);  // exact run ends along anchor chains
-    void set_sss(const pos_t* S_any, u64 count, bool runs);  // an externally built (sharded) sync set
+    void set_sss(const u64* S_any, u64 count, bool runs);  // an externally built (sharded) sync set
     void build_sss_range(u64 first, u64 end, u64 base, u64 window);  // csrc/sss.hip
     void build_sa_s(const u8* T);
     void build_lcp_rmq(const u8* T);

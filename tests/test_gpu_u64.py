@@ -164,6 +164,18 @@ def test_u64_session_rejects_32bit_accessors(session64, lz):
         s.factorize_exact()
     with pytest.raises(lz.Lz77SssError):
         s.huffman()
+    # the accessors in the 32-bit layout, and the container of a skip_phrases stream
+    lib, buf, c = lz.load_library(), np.empty(1 << 16, np.uint32), ctypes.c_uint64()
+    ptr = buf.ctypes.data_as(ctypes.c_void_p)
+    for call in (lambda: lib.lz77sss_session_get_factors(s._h, ptr, buf.size // 2),
+                 lambda: lib.lz77sss_session_get_sss(s._h, ptr, buf.size),
+                 lambda: lib.lz77sss_session_get_lpf(s._h, ptr, buf.size // 3, ctypes.byref(c))):
+        with pytest.raises(lz.Lz77SssError, match="not available on a pos_t = uint64_t session") as e:
+            lz._check(call())
+        assert e.value.code == lz.EINVAL
+    s.factorize(fact_mode=lz.SKIP_PHRASES)
+    with pytest.raises(lz.Lz77SssError, match="not available on a pos_t = uint64_t session"):
+        s.ssszip_gapped()
 
 
 @pytest.mark.slow
