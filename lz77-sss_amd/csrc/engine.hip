@@ -210,8 +210,8 @@ void engine::prepare_phrases(int phr_mode, bool external_sss) {
 void engine::release_greedy_buffers() {
     fact.release(); tmp_greedy.release(); chunk_buf.release(); chunk_buf2.release(); rem_buf.release();
     add_keys32.release(); add_pos.release(); dirty_in.release(); dirty_out.release(); dirty_sorted.release();
-    tmp_greedy2.release(); tmp_greedy3.release(); add_keys.release(); add_keys2.release();
-    seg_in_buf.release(); seg_out_buf.release(); seg_ids.release(); irank.release(); ekeys.release();
+    tmp_greedy2.release(); add_keys.release(); add_keys2.release();
+    irank.release(); ekeys.release();
     evals.release(); ekeys2.release(); evals2.release(); occ_buf.release(); ist.release(); iend.release();
     ipos_buf.release(); iposr_buf.release(); tail_ins_buf.release(); seg_offs.release();
     g_sin.release(); g_sout.release(); g_valid.release(); g_cs.release(); g_tailc.release();

@@ -2106,251 +2106,385 @@ __global__ __launch_bounds__(LS_T) void k_ls_rank(KF kf, const u32* __restrict__
     }
 }
 
-// gap-index slot count (the carried table's entries) of the current phrases
-u64 engine::carried_entries(int log2_override) {
-    const pos_t N = (pos_t)n;
-    const u32 m = num_phr;
-    pos_t* P = lpf.get((u64)(m + 1) * 3);
-    k_put3<<<1, 1, 0, st>>>(P + 3 * (u64)m, N, N + 1, 0);
-    u64 num_gaps = 1;
+// ---------------------------------------------------------------------------
+// host side of the emitter: the knobs and parameters of a call, the helpers
+// that need no window state, a window's state and steps (greedy_window), engine::factorize_greedy
+
+// the environment knobs of factorize_greedy and its steps, read once per call (the tests
+// change them between the calls of one process)
+struct greedy_knobs {
+    // test knobs of the chain-insert kernels: a small long-range list and a short "long" range
+    // make the overflow path run
+    u32 lng_cap, long_words;
+    u32 CH;                 // LZ77SSS_GAP_CHUNK / LZ77SSS_NO_CHUNK: tuning knob (walk length per segment)
+    int max_outer;          // LZ77SSS_GREEDY_MAX_OUTER: test knob (0: sequential only)
+    u64 pred_sorted_min;    // LZ77SSS_PRED_SORTED_MIN
+    u64 window;             // LZ77SSS_GREEDY_WINDOW (0: not set)
+    int pred;               // LZ77SSS_PRED: 1, LZ77SSS_NO_PRED: 0, neither: -1
+    u32 slot_chunk;         // LZ77SSS_SLOT_CHUNK: short chunks (test/tuning knob, <= SLOT_CHUNK_LONG)
+    int slot_chunk_sh;      // LZ77SSS_SLOT_CHUNK_SH
+    bool no_dense, no_lsd, lsd_check, pred_radix, no_iposr;  // base build
+    bool ls_blocksort, ls_rank;                              // lsd_sort: either form for every pass
+    bool no_fast_check, debug_jump;
+    greedy_knobs() {
+        auto set = [](const char* k) { return std::getenv(k) != nullptr; };
+        const char* e = std::getenv("LZ77SSS_TEST_LNG_CAP");
+        lng_cap = e ? (u32)std::max<long>(0, std::atol(e)) : 0xFFFFFFFFu;
+        e = std::getenv("LZ77SSS_TEST_LONG_WORDS");
+        long_words = e ? (u32)std::max<long>(1, std::atol(e)) : 2048u;
+        e = std::getenv("LZ77SSS_GAP_CHUNK");
+        CH = set("LZ77SSS_NO_CHUNK") ? 0x0FFFFFFFu : e ? (u32)std::max(16, std::atoi(e)) : 512u;
+        e = std::getenv("LZ77SSS_GREEDY_MAX_OUTER");
+        max_outer = e ? std::max(0, std::atoi(e)) : 256;
+        e = std::getenv("LZ77SSS_PRED_SORTED_MIN");
+        pred_sorted_min = e ? std::strtoull(e, nullptr, 10) : (1ull << 27);
+        e = std::getenv("LZ77SSS_GREEDY_WINDOW");
+        window = e ? std::max<u64>(4096, std::strtoull(e, nullptr, 10)) : 0;
+        pred = set("LZ77SSS_PRED") ? 1 : set("LZ77SSS_NO_PRED") ? 0 : -1;
+        e = std::getenv("LZ77SSS_SLOT_CHUNK");
+        slot_chunk = e ? std::max(8u, std::min<u32>(SLOT_CHUNK_LONG, (u32)std::atoi(e))) : SLOT_CHUNK_SHORT;
+        e = std::getenv("LZ77SSS_SLOT_CHUNK_SH");
+        slot_chunk_sh = e ? std::atoi(e) : 18;
+        no_dense = set("LZ77SSS_NO_DENSE");
+        no_lsd = set("LZ77SSS_NO_LSD");
+        lsd_check = set("LZ77SSS_LSD_CHECK");
+        pred_radix = set("LZ77SSS_PRED_RADIX");
+        no_iposr = set("LZ77SSS_NO_IPOSR");
+        ls_blocksort = set("LZ77SSS_LS_BLOCKSORT");
+        ls_rank = set("LZ77SSS_LS_RANK");
+        no_fast_check = set("LZ77SSS_NO_FAST_CHECK");
+        debug_jump = set("LZ77SSS_DEBUG_JUMP");
+    }
+};
+
+// phrase statistics -> gap-index parameters (lz77_sss.hpp:420-461); writes the sentinel P[m].
+// cached: take the statistics the phrase builder left (build_lpf_opt: sentinel written too)
+struct phrase_stats {
     pos_t len_lpf_phr = 0;
-    if (m > 0) {
-        u64* acc = counters64.get(16) + 2;
-        LZ_HIP(hipMemsetAsync(acc, 0, 16, st));
-        k_phrase_info<<<cdiv(m, 256), 256, 0, st>>>(P, m, N, acc);
+    u64 num_gaps = 1;
+    gap_params_h gp;
+};
+static phrase_stats greedy_phrase_stats(engine& E, pos_t* P, int log2_override, bool cached) {
+    const pos_t N = (pos_t)E.n;
+    const u32 m = E.num_phr;
+    const bool have = cached && E.phr_info.valid;
+    phrase_stats ps;
+    if (!have) k_put3<<<1, 1, 0, E.st>>>(P + 3 * (u64)m, N, N + 1, 0);
+    if (have && m > 0) {
+        ps.len_lpf_phr = (pos_t)E.phr_info.len;
+        ps.num_gaps = E.phr_info.gaps;
+    } else if (m > 0) {
+        u64* acc = E.counters64.get(16) + 2;
+        LZ_HIP(hipMemsetAsync(acc, 0, 16, E.st));
+        k_phrase_info<<<cdiv(m, 256), 256, 0, E.st>>>(P, m, N, acc);
         u64 h2[2];
-        hread rb(st);
+        hread rb(E.st);
         rb.add(h2, acc, 2);
         rb.sync();
-        len_lpf_phr = (pos_t)h2[0];
-        num_gaps = h2[1];
+        ps.len_lpf_phr = (pos_t)h2[0];
+        ps.num_gaps = h2[1];
     }
-    gap_params_h gp = choose_gap_params(N, m, len_lpf_phr, num_gaps);
-    if (log2_override > 0) gp.log2_size_h = (u32)log2_override;
-    return 1ull << gp.log2_size_h;
+    ps.gp = choose_gap_params(N, m, ps.len_lpf_phr, ps.num_gaps);
+    if (log2_override > 0) ps.gp.log2_size_h = (u32)log2_override;
+    return ps;
 }
 
-u64 engine::factorize_greedy(const u8* T, u32 rk_seed, int log2_override, greedy_block* blk) {
-    const bool dbg = debug_enabled();
-    double t_mark = now_ms();
-    auto lap = [&](const char* what) {
+// gap-index slot count (the carried table's entries) of the current phrases
+u64 engine::carried_entries(int log2_override) {
+    pos_t* P = lpf.get((u64)(num_phr + 1) * 3);
+    return 1ull << greedy_phrase_stats(*this, P, log2_override, false).gp.log2_size_h;
+}
+
+// the influence tables depend only on (bases, pattern lengths): uploaded once per change
+static u128* upload_negpow(engine& E, const std::array<u64, 5>& bases, const gap_params_h& gp) {
+    u128* d_negpow = (u128*)E.tmp_greedy.get(5 * 256 * sizeof(u128));
+    std::array<u64, 10> key;
+    for (int x = 0; x < 5; x++) { key[x] = bases[x]; key[5 + x] = gp.patt_lens[x]; }
+    if (key != E.negpow_key || d_negpow != E.negpow_dev) {
+        std::vector<u128> negpow(5 * 256);
+        for (int x = 0; x < 5; x++) {
+            const u128 bp = powmod107_host(bases[x], gp.patt_lens[x]);
+            const u128 nbp = (P107 - bp) % P107;
+            negpow[x * 256] = 0;
+            for (int o = 1; o < 256; o++) negpow[x * 256 + o] = mod107(negpow[x * 256 + o - 1] + nbp);
+        }
+        LZ_HIP(hipMemcpyAsync(d_negpow, negpow.data(), 5 * 256 * sizeof(u128), hipMemcpyHostToDevice, E.st));
+        LZ_HIP(hipStreamSynchronize(E.st));  // (the host vector goes out of scope)
+        E.negpow_key = key;
+        E.negpow_dev = d_negpow;
+    }
+    return d_negpow;
+}
+
+// slot -> first of the mk sorted keys (key(t): slot of sorted entry t) with that slot or a later one
+template <class KEY>
+static void build_buckets(engine& E, u32 nslots, KEY key, u64 mk, dbuf<u32>& bk) {
+    hipStream_t st = E.st;
+    u32* b = bk.get((u64)nslots + 1);
+    if (mk * 16 >= nslots) {
+        u32* rev = E.g_brev.get(2 * ((u64)nslots + 1));
+        u32* scn = rev + nslots + 1;
+        LZ_HIP(hipMemsetAsync(rev, 0xFF, ((u64)nslots + 1) * 4, st));
+        k_bucket_heads<<<cdiv(mk + 1, 256), 256, 0, st>>>(key, mk, nslots, rev);
+        size_t tb = 0;
+        LZ_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, tb, rev, scn, min_u32_op{}, (int)(nslots + 1), st));
+        u8* t = E.scan_tmp.get(tb);
+        LZ_HIP(hipcub::DeviceScan::InclusiveScan(t, tb, rev, scn, min_u32_op{}, (int)(nslots + 1), st));
+        k_unreverse<<<cdiv((u64)nslots + 1, 256), 256, 0, st>>>(scn, nslots, b);
+    } else {
+        k_bucket_search<<<cdiv((u64)nslots + 1, 256), 256, 0, st>>>(key, mk, nslots, b);
+    }
+}
+
+// LSD sort of m entries on `bits` key bits (pass-0 keys from kf0): entry ids to vout, the first
+// sorted index of every key to head (pre-set to NONE); ka / va: scratch for the middle passes
+template <class KF>
+static void lsd_sort(engine& E, const greedy_knobs& K, KF kf0, u64 m, u32 bits, u32* ka, u32* va, u32* vout, u32* head,
+                     u32 nkeys) {
+    hipStream_t st = E.st;
+    const u32 npass = std::max<u32>(1, (bits + LS_DB - 1) / LS_DB);
+    if (npass > LS_MAXP) throw error(-6, "lsd_sort: too many key bits");
+    const u32 ntile = cdiv(m, LS_TILE);
+    const u64 per = (u64)LS_NB * ntile;
+    u32* H = E.g_ls_h.get(per + 1);
+    u32* Gs = E.g_ls_g.get(per + 1);
+    // the first pass (entry order: many distinct digits per wave) block-sorts its tiles, the
+    // later ones (inputs sorted on the lower digits: few per wave) rank by ballots
+    // (rr 13-bit dense keys: pass 0 278 vs 369 us, pass 1 167 vs 284 us); LZ77SSS_LS_BLOCKSORT /
+    // LZ77SSS_LS_RANK force either for every pass
+    auto use_bsort = [&](u32 p) { return K.ls_blocksort || (!K.ls_rank && p == 0); };
+    const bool bsort = use_bsort(npass - 1);  // the last pass: heads in the block-sort kernel
+    // ping-pong: pass p reads what pass p - 1 wrote (the ranking form writes the last pass's
+    // keys too, for the key heads)
+    const bool kb1 = npass > 2 || (head && !bsort && npass > 1);
+    u32 *kb[2] = {ka, kb1 ? E.g_predk.get(m + 1) : nullptr}, *vb[2] = {va, npass > 2 ? E.g_ids2.get(m + 1) : nullptr};
+    u32* klast = nullptr;
+    for (u32 p = 0; p < npass; p++) {
+        const bool first = p == 0, lastp = p + 1 == npass;
+        u32 *ko = kb[p & 1], *vo = lastp ? vout : vb[p & 1];
+        const u32 *ki = kb[(p + 1) & 1], *vi = vb[(p + 1) & 1];
+        const ls_plain kp{ki};
+        if (first) k_ls_hist<KF, false><<<ntile, LS_T, 0, st>>>(kf0, m, p, ntile, H);
+        else k_ls_hist<ls_plain, true><<<ntile, LS_T, 0, st>>>(kp, m, p, ntile, H);
+        excl_sum64(H, Gs, 0u, per, E.scan_tmp, st);
+        if (use_bsort(p)) {
+            if (first && lastp)
+                k_ls_scatter<KF, true, true><<<ntile, LS_T, 0, st>>>(kf0, ki, vi, m, p, ntile, Gs, ko, vo, head);
+            else if (first)
+                k_ls_scatter<KF, true, false><<<ntile, LS_T, 0, st>>>(kf0, ki, vi, m, p, ntile, Gs, ko, vo, head);
+            else if (lastp)
+                k_ls_scatter<ls_plain, false, true><<<ntile, LS_T, 0, st>>>(kp, ki, vi, m, p, ntile, Gs, ko, vo, head);
+            else
+                k_ls_scatter<ls_plain, false, false><<<ntile, LS_T, 0, st>>>(kp, ki, vi, m, p, ntile, Gs, ko, vo, head);
+        } else {
+            u32* kw = (lastp && !head) ? nullptr : ko;
+            if (lastp) klast = kw;
+            if (first && lastp)
+                k_ls_rank<KF, true, true><<<ntile, LS_T, 0, st>>>(kf0, ki, vi, m, p, ntile, Gs, kw, vo);
+            else if (first)
+                k_ls_rank<KF, true, false><<<ntile, LS_T, 0, st>>>(kf0, ki, vi, m, p, ntile, Gs, kw, vo);
+            else if (lastp)
+                k_ls_rank<ls_plain, false, true><<<ntile, LS_T, 0, st>>>(kp, ki, vi, m, p, ntile, Gs, kw, vo);
+            else
+                k_ls_rank<ls_plain, false, false><<<ntile, LS_T, 0, st>>>(kp, ki, vi, m, p, ntile, Gs, kw, vo);
+        }
+    }
+    if (head && !bsort) k_dense_heads<<<cdiv(cdiv(m + 1, 4), 256), 256, 0, st>>>(klast, m, nkeys, head);
+    LZ_HIP(hipGetLastError());
+}
+
+// LZ77SSS_LSD_CHECK: the dense-id sort of the ne5 base entries again by rocprim into scratch,
+// compared entry by entry with what lsd_sort wrote (svals, dstart)
+static void lsd_check(engine& E, u32* keys, u64 ne5, u32* pbm, u32* pwp, u64 npw, u32 D, u32 dense_bits, u32* svals,
+                      u32* dstart) {
+    hipStream_t st = E.st;
+    u32* dk = E.g_sdk.get(ne5 + 1);
+    u32* ck = E.g_predk.get(ne5 + 1);
+    u32* cv = E.g_ids2.get(ne5 + 1);
+    k_dense_keys<<<cdiv(cdiv(ne5, 4), 256), 256, 0, st>>>(keys, ne5, pbm, pwp, dk);
+    size_t tb = 0;
+    const rocprim::counting_iterator<u32> ids(0);
+    LZ_HIP(rocprim::radix_sort_pairs(nullptr, tb, dk, ck, ids, cv, (size_t)ne5, 0u, dense_bits, st));
+    u8* t = E.scan_tmp.get(tb);
+    LZ_HIP(rocprim::radix_sort_pairs(t, tb, dk, ck, ids, cv, (size_t)ne5, 0u, dense_bits, st));
+    u32* ds2 = E.g_pcnt.get(std::max<u64>(npw + 1, (u64)D + 2));
+    k_pred_heads<<<cdiv(ne5 + 1, 256), 256, 0, st>>>(ck, cv, ne5, D, nullptr, ds2);
+    u64* r = (u64*)E.g_cut.get(sizeof(chain_cut) + 256) + 20;
+    const u64 init[4] = {~0ull, 0, ~0ull, 0};
+    LZ_HIP(hipMemcpyAsync(r, init, 32, hipMemcpyHostToDevice, st));
+    k_first_diff_u32<<<cdiv(ne5, 256), 256, 0, st>>>(svals, cv, ne5, r);
+    k_first_diff_u32<<<cdiv((u64)D + 1, 256), 256, 0, st>>>(dstart, ds2, (u64)D + 1, r + 2);
+    u64 h[4];
+    LZ_HIP(hipMemcpyAsync(h, r, 32, hipMemcpyDeviceToHost, st));
+    LZ_HIP(hipStreamSynchronize(st));
+    std::fprintf(stderr, "[lz77sss-lsd-check] m=%llu D=%u bits=%u: svals diff=%llu first=%lld, dstart diff=%llu first=%lld\n",
+                 (unsigned long long)ne5, D, dense_bits, (unsigned long long)h[1], (long long)h[0],
+                 (unsigned long long)h[3], (long long)h[2]);
+    if (h[1] || h[3]) {
+        u32 a[8], b[8];
+        const u64 f = h[1] ? std::min<u64>(h[0], ne5 - 8) : 0;
+        LZ_HIP(hipMemcpy(a, svals + f, 32, hipMemcpyDeviceToHost));
+        LZ_HIP(hipMemcpy(b, cv + f, 32, hipMemcpyDeviceToHost));
+        for (int q = 0; q < 8; q++) std::fprintf(stderr, "  [%llu] lsd %u rocprim %u\n", (unsigned long long)(f + q), a[q], b[q]);
+    }
+}
+
+// what the windows of one factorize_greedy call share
+struct greedy_call {
+    greedy_knobs K;
+    const u8* T;
+    pos_t N;
+    u32 m;  // phrases; P[m] = sentinel
+    pos_t* P;
+    gap_params_h gp;
+    gap_cfg G;
+    u32 zmask0;        // fingerprints zeroed from the start (pattern length >= N)
+    u64 nslots_all;    // gap-index slots
+    pos_t* Hs;         // the carried table (several windows, or a block), else null
+    lce_view Lv;
+    greedy_block* blk;
+    // same-slot predecessors (pred5) pay for their scatter when the walks make many
+    // lookups: short gaps (many factors per gap position).  Texts with few, long gaps
+    // (long factors, few lookups) search the buckets instead.  LZ77SSS_PRED /
+    // LZ77SSS_NO_PRED force either path (tests).
+    int use_pred;
+    bool dbg;
+    mutable double t_mark;
+    // debug timing of the step that ends here; synchronizes only when debug is on
+    void lap(hipStream_t st, const char* what) const {
         if (!dbg) return;
         LZ_HIP(hipStreamSynchronize(st));
         const double t = now_ms();
         std::fprintf(stderr, "[lz77sss-debug]   %-28s %9.3f ms\n", what, t - t_mark);
         t_mark = t;
-    };
-    const pos_t N = (pos_t)n;
-    const u32 m = num_phr;  // phrases; P[m] = sentinel
-    pos_t* P = lpf.get((u64)(m + 1) * 3);
-    // ---- phrase statistics -> parameters (lz77_sss.hpp:420-461)
-    u64 num_lpf = m, num_gaps = 1;
-    pos_t len_lpf_phr = 0;
-    if (!phr_info.valid) k_put3<<<1, 1, 0, st>>>(P + 3 * (u64)m, N, N + 1, 0);
-    if (phr_info.valid && m > 0) {
-        len_lpf_phr = (pos_t)phr_info.len;  // (build_lpf_opt: statistics and sentinel done)
-        num_gaps = phr_info.gaps;
-    } else if (m > 0) {
-        u64* acc = counters64.get(16) + 2;
-        LZ_HIP(hipMemsetAsync(acc, 0, 16, st));
-        k_phrase_info<<<cdiv(m, 256), 256, 0, st>>>(P, m, N, acc);
-        u64 h2[2];
-        hread rb(st);
-        rb.add(h2, acc, 2);
-        rb.sync();
-        len_lpf_phr = (pos_t)h2[0];
-        num_gaps = h2[1];
     }
-    gap_params_h gp = choose_gap_params(N, num_lpf, len_lpf_phr, num_gaps);
-    if (log2_override > 0) gp.log2_size_h = (u32)log2_override;
-    // bases: rk_prime::random64(257, 2^20-1) from mt19937_64(rk_seed) (rolling_hash.hpp:127-130)
-    std::array<u64, 5> bases;
-    {
-        std::mt19937_64 g(rk_seed);
-        for (int i = 0; i < 5; i++) bases[i] = std::uniform_int_distribution<u64>(257, (1ull << 20) - 1)(g);
-    }
-    // the influence tables depend only on (bases, pattern lengths): uploaded once per change
-    u128* d_negpow = (u128*)tmp_greedy.get(5 * 256 * sizeof(u128));
-    {
-        std::array<u64, 10> key;
-        for (int x = 0; x < 5; x++) { key[x] = bases[x]; key[5 + x] = gp.patt_lens[x]; }
-        if (key != negpow_key || d_negpow != negpow_dev) {
-            std::vector<u128> negpow(5 * 256);
-            for (int x = 0; x < 5; x++) {
-                const u128 bp = powmod107_host(bases[x], gp.patt_lens[x]);
-                const u128 nbp = (P107 - bp) % P107;
-                negpow[x * 256] = 0;
-                for (int o = 1; o < 256; o++) negpow[x * 256 + o] = mod107(negpow[x * 256 + o - 1] + nbp);
-            }
-            LZ_HIP(hipMemcpyAsync(d_negpow, negpow.data(), 5 * 256 * sizeof(u128), hipMemcpyHostToDevice, st));
-            LZ_HIP(hipStreamSynchronize(st));  // (the host vector goes out of scope)
-            negpow_key = key;
-            negpow_dev = d_negpow;
-        }
+};
+
+// one window [a, bw) of the chain: its state and its steps, in call order in run()
+struct greedy_window {
+    engine& E;
+    const greedy_call& C;
+    const hipStream_t st;
+    const int nwin;  // the window's index (debug output)
+    // geometry: non-last windows end below the tail region (nt) and leave >= 4096 positions
+    const seg_in entry;  // the chain state at a
+    const pos_t a, bw;
+    const bool last;
+    const pos_t off;  // bitmap origin (word aligned)
+    const u64 nw;     // bitmap words (a zero word past the end)
+    const unsigned gw, bmb_blocks;
+    const pos_t hi_ins;  // inserts recorded in the window bitmaps: [a, hi_ins)
+    const u32 nslots;
+    // segment table
+    u32 nseg0 = 0, cap = 0, nseg = 0, c0 = 0;
+    seg_tab S{};
+    seg_in entry_in{};  // the exact entry of the window as the completion path sees it
+    u32* ids = nullptr;
+    u32* d_cnt = nullptr;
+    // bitmaps: I (current speculation), I' (what the chain inserted), Ib (base set), scratch, and
+    // A (the main added list's positions).  bmI / bmI2 follow g_bmI / g_bmI2 (swap_I)
+    u32 *bmI = nullptr, *bmI2 = nullptr, *bmIb = nullptr, *bmT = nullptr, *bmA = nullptr;
+    walk_ctx W{};
+    // base set (entries sorted by slot) and delta.  The main added list is rebuilt rarely
+    // (membership of its positions is read from the I bitmap); positions that join later and are
+    // missing from it go to the small extra list
+    u64 nb = 0, na_main = 0;
+    bool bmA_zero = false;  // the main list is empty and bmA was not computed (I within the base set)
+    // I_fresh: I was set by set_state(true) and not changed since (I lies within the base set), so
+    // I' == I is decided by two checks over the chain's inserts and the base ranks (i_cnt[0]:
+    // inserts outside I, i_cnt[1]: positions of I not inserted) instead of a full-length xor and count
+    bool I_fresh = false;
+    u32* i_cnt = nullptr;
+    // bounded completion (k_seq_walk): counters, the chain cut, the first changed position
+    u64* d_sq = nullptr;
+    chain_cut* d_cutp = nullptr;
+    u64* d_y0 = nullptr;
+    // the chain of the current outer round: nall nodes (the last one the tail's, if any)
+    chain_status cs{};
+    chain_status* d_cs = nullptr;
+    jump_levels JL{};
+    bool tail = false;
+    u32 nall = 0, nchain = 0;
+    u32* chain = nullptr;
+    u64* offs = nullptr;  // factor offsets of the chain nodes
+    u64 chain_fact = 0, tail_count = 0, tail_nins = 0;
+    // results: fact[0, wfact), the window exit (the chain state at the first hand-over point
+    // >= bw), redo (the chain reaches the tail region: walk again as the last window), counters
+    u64 wfact = 0, walked_total = 0;
+    int outer = 0, rounds_total = 0;
+    seg_in exit_in{};
+    bool redo = false;
+
+    greedy_window(engine& e, const greedy_call& c, const seg_in& en, pos_t bw_, int nwin_)
+        : E(e), C(c), st(e.st), nwin(nwin_), entry(en), a(en.start), bw(bw_), last(bw_ == c.N), off(a & ~(pos_t)31),
+          nw((u64)(bw - off) / 32 + 2), gw(cdiv(nw, 256)), bmb_blocks((unsigned)std::max<u64>(1, (nw + BMB - 1) / BMB)),
+          hi_ins(std::min<pos_t>(bw, c.G.nt)), nslots(c.G.mask + 1) {}
+
+    void bind_tab() {
+        S.sin = E.g_sin.p; S.sout = E.g_sout.p; S.valid = E.g_valid.p; S.succ = E.g_succ.p; S.cap = cap;
+        S.stash = E.g_stash.p;
     }
 
-    stats.assign(28, 0);
-    stats[0] = s; stats[1] = has_runs; stats[2] = num_lpf; stats[3] = len_lpf_phr; stats[4] = num_gaps;
-    for (int x = 0; x < 5; x++) stats[5 + x] = gp.patt_lens[x];
-    stats[10] = gp.roll_threshold; stats[11] = gp.log2_size_h;
-
-    gap_cfg G{};
-    G.n = N;
-    G.nt = N > 64 ? N - 64 : 0;
-    for (int x = 0; x < 5; x++) { G.lens[x] = gp.patt_lens[x]; G.base[x] = bases[x]; }
-    G.thr = gp.roll_threshold;
-    G.mask = (u32)((1ull << gp.log2_size_h) - 1);
-    G.negpow = d_negpow;
-    u32 zmask0 = 0;
-    for (int x = 0; x < 5; x++) zmask0 |= (G.lens[x] >= N) ? (1u << x) : 0u;  // reinit(0) at construction
-    // test knobs of the chain-insert kernels, read once per call: a small long-range list and a
-    // short "long" range make the overflow path run
-    const u32 knob_lng_cap = [] {
-        const char* e = std::getenv("LZ77SSS_TEST_LNG_CAP");
-        return e ? (u32)std::max<long>(0, std::atol(e)) : 0xFFFFFFFFu;
-    }();
-    const u32 knob_long_words = [] {
-        const char* e = std::getenv("LZ77SSS_TEST_LONG_WORDS");
-        return e ? (u32)std::max<long>(1, std::atol(e)) : 2048u;
-    }();
-    const char* ch_env = std::getenv("LZ77SSS_GAP_CHUNK");  // tuning knob (walk length per segment)
-    const u32 CH = std::getenv("LZ77SSS_NO_CHUNK") ? 0x0FFFFFFFu : ch_env ? (u32)std::max(16, std::atoi(ch_env)) : 512u;
-    const char* mo_env = std::getenv("LZ77SSS_GREEDY_MAX_OUTER");  // test knob (0: sequential only)
-    const int max_outer = mo_env ? std::max(0, std::atoi(mo_env)) : 256;
-    const u64 nslots_all = (u64)G.mask + 1;
-    const char* psm = std::getenv("LZ77SSS_PRED_SORTED_MIN");
-    const u64 pred_sorted_min = psm ? std::strtoull(psm, nullptr, 10) : (1ull << 27);
-
-    // ---- windows (DESIGN.md 4.5): the chain is walked window by window; a window gets the
-    // exact chain state at its start and the table of the last insert per slot before it
-    // (pos + 1, 0 = none), and hands both on.  Windows bound the gap-index entry ids
-    // (32-bit) and every position-indexed structure to the window's span.  One window
-    // covers the text unless its base set would not fit (or LZ77SSS_GREEDY_WINDOW asks).
-    const u64 est_base = (u64)(N - len_lpf_phr) + 49ull * (m + 1);  // gap positions + queries + short phrases
-    u64 WS = N;
-    if (const char* we = std::getenv("LZ77SSS_GREEDY_WINDOW")) {
-        WS = std::max<u64>(4096, std::strtoull(we, nullptr, 10));
-    } else if (est_base * 5 >= (1ull << 31)) {
-        // windows of ~2^31 / 10 base positions (uniform gap density assumed; a window whose base
-        // set still overflows the ids fails loudly below)
-        WS = std::max<u64>(1ull << 20, (u64)((double)N * ((double)(1ull << 31) / 10.0) / (double)est_base));
-    }
-    // a block of a sharded factorization: [blk->start, blk->end) from the given chain state
-    const pos_t target_end = blk ? blk->end : N;
-    if (blk && (blk->end > N || blk->start >= blk->end || (blk->end < N && (u64)blk->end + 4096 > (u64)G.nt)))
-        throw error(LZ77SSS_EINVAL, "greedy block: need start < end and end == n or end <= n - 4160");
-    const bool multi = WS < (u64)N;
-    const bool carry = multi || blk;
-    pos_t* Hs = nullptr;
-    if (carry) {
-        if (blk && blk->carried && g_Hs.cap < nslots_all)
-            throw error(LZ77SSS_EINVAL, "greedy block: carried table not loaded (size it with carried_entries)");
-        Hs = g_Hs.get(nslots_all);
-        if (!(blk && blk->carried)) LZ_HIP(hipMemsetAsync(Hs, 0, nslots_all * sizeof(pos_t), st));
-    }
-    if (blk && !blk->carried && blk->seed && blk->start > 0) {
-        // a lead-in of a speculative block: the table seeded from the gap positions before it
-        u32* cnt = g_tmp1.get(m + 2);
-        u32* off = g_tmp2.get(m + 2);
-        k_seed_counts<<<cdiv(m + 1, 256), 256, 0, st>>>(P, m, blk->start, cnt);
-        const u32 nch = excl_scan(cnt, off, m + 1, scan_tmp, st);
-        if (nch) k_seed_slots<<<cdiv(5ull * nch, 256), 256, 0, st>>>(T, G, P, m, blk->start, off, nch, Hs);
-        k_seed_queries<<<cdiv(5ull * (m + 1), 256), 256, 0, st>>>(T, G, P, m, blk->start, Hs);
-        LZ_HIP(hipGetLastError());
-    }
-    if (blk && spec_track && nslots_all > spec_m)
-        throw error(LZ77SSS_EINVAL, "speculative block: the carried table changed size since spec_begin");
-    seg_in entry{0, 0, 0, zmask0, N};
-    if (blk) {
-        entry.start = blk->start;
-        entry.idxpos = blk->idxpos;
-        entry.zmask = blk->zmask;
-    }
-    u64 total_fact = 0, walked_all = 0;
-    int outer_all = 0, rounds_all = 0, nwin = 0;
-    u32 nseg_last = 0, nseg0_all = 0;
-    lce_view Lv = view(T);
-    // a non-last window (or block) whose chain reaches the tail region (a gap factor
-    // longer than the >= 4096 positions left after the window end) is walked again as the
-    // last window: the tail model needs every insert in the tail region before its start
-    bool force_last = false;
-
-    for (;;) {
-        const pos_t a = entry.start;
-        // the window [a, bw): non-last windows end below the tail region (nt) and leave >= 4096 positions
-        pos_t bw = force_last ? N : target_end;
-        if (!force_last && WS < (u64)(target_end - a) && (u64)a + WS + 4096 <= (u64)G.nt) bw = (pos_t)(a + WS);
-        const bool last = bw == N;
-        bool redo = false;
-        const pos_t off = a & ~(pos_t)31;  // bitmap origin (word aligned)
-        const u64 nw = (u64)(bw - off) / 32 + 2;  // bitmap words (a zero word past the end)
-        const unsigned gw = cdiv(nw, 256);
-        const unsigned bmb_blocks = (unsigned)std::max<u64>(1, (nw + BMB - 1) / BMB);
-        const pos_t hi_ins = std::min<pos_t>(bw, G.nt);  // inserts recorded in the window bitmaps: [a, hi_ins)
-
-        // ---- default segments: gaps (clipped to the window) + chunk boundaries of long gaps
-        u32* cnt_seg = g_tmp1.get(m + 2);
-        u32* cnt_cb = g_tmp2.get(m + 2);
-        u32* off_seg = g_tmp3.get(m + 2);
-        u32* off_cb = g_tmp4.get(m + 2);
+    // ---- default segments: gaps (clipped to the window) + chunk boundaries of long gaps; the
+    // window entry; the bitmaps; the lookup context
+    void setup() {
+        const u32 m = C.m, CH = C.K.CH;
+        pos_t* const P = C.P;
+        const pos_t N = C.N;
+        const gap_cfg& G = C.G;
+        u32* cnt_seg = E.g_tmp1.get(m + 2);
+        u32* cnt_cb = E.g_tmp2.get(m + 2);
+        u32* off_seg = E.g_tmp3.get(m + 2);
+        u32* off_cb = E.g_tmp4.get(m + 2);
         k_gap_counts<<<cdiv(m + 1, 256), 256, 0, st>>>(P, m, CH, a, bw, G.nt, cnt_seg, cnt_cb);
-        excl_scan_nr(cnt_seg, off_seg, m + 1, scan_tmp, st);
-        excl_scan_nr(cnt_cb, off_cb, m + 1, scan_tmp, st);
-        u32 nseg0, ncb;
+        excl_scan_nr(cnt_seg, off_seg, m + 1, E.scan_tmp, st);
+        excl_scan_nr(cnt_cb, off_cb, m + 1, E.scan_tmp, st);
+        u32 ncb;
         {
             hread rb(st);
             rb.add(&nseg0, off_seg + m + 1);
             rb.add(&ncb, off_cb + m + 1);
             rb.sync();
         }
-        pos_t* cbv = g_cbv.get(ncb + 1);
+        pos_t* cbv = E.g_cbv.get(ncb + 1);
         if (ncb) k_gap_cbv<<<cdiv(ncb, 256), 256, 0, st>>>(P, m, CH, a, bw, off_cb, ncb, cbv);
-        u32 cap = nseg0 + nseg0 / 2 + (1u << 16);
-        seg_tab S{};
-        auto bind_tab = [&]() {
-            S.sin = g_sin.p; S.sout = g_sout.p; S.valid = g_valid.p; S.succ = g_succ.p; S.cap = cap;
-            S.stash = g_stash.p;
-        };
-        g_sin.get(cap); g_sout.get(cap); g_valid.get(cap); g_succ.get(cap);
-        g_stash.get((u64)cap * 2 * STASH_CAP);
+        cap = nseg0 + nseg0 / 2 + (1u << 16);
+        E.g_sin.get(cap); E.g_sout.get(cap); E.g_valid.get(cap); E.g_succ.get(cap);
+        E.g_stash.get((u64)cap * 2 * STASH_CAP);
         bind_tab();
         {
             // the position -> segment map is cleared sparsely after each window (k_seg_at_clear);
             // a fresh or reallocated map, or one left dirty by a failed call, is cleared densely
             const u64 span = (u64)(bw - a) + 1;
-            u32* prev = g_seg_at.p;
-            S.seg_at = g_seg_at.get(span);
-            if (S.seg_at != prev || !seg_at_clean || seg_at_n < span) {
-                LZ_HIP(hipMemsetAsync(S.seg_at, 0xFF, g_seg_at.cap * 4, st));
-                seg_at_n = g_seg_at.cap;
+            u32* prev = E.g_seg_at.p;
+            S.seg_at = E.g_seg_at.get(span);
+            if (S.seg_at != prev || !E.seg_at_clean || E.seg_at_n < span) {
+                LZ_HIP(hipMemsetAsync(S.seg_at, 0xFF, E.g_seg_at.cap * 4, st));
+                E.seg_at_n = E.g_seg_at.cap;
             }
-            seg_at_clean = false;
+            E.seg_at_clean = false;
         }
         S.segoff = a;
-        S.nseg = (u32*)counters64.get(16);  // [0] nseg/err, [1] c0, [2..3] phrase info, [4..] entry seg_in
+        S.nseg = (u32*)E.counters64.get(16);  // [0] nseg/err, [1] c0, [2..3] phrase info, [4..] entry seg_in
         S.err = S.nseg + 1;
         k_set_u32x2<<<1, 1, 0, st>>>(S.nseg, nseg0, 0);
-        S.cbv = cbv; S.ncb = ncb; S.P = P; S.m = m; S.N = bw; S.zmask0 = zmask0;
+        S.cbv = cbv; S.ncb = ncb; S.P = P; S.m = m; S.N = bw; S.zmask0 = C.zmask0;
         if (nseg0) k_gap_segs<<<cdiv(nseg0, 256), 256, 0, st>>>(S, CH, off_seg, nseg0);
-        u32* d_c0 = (u32*)(counters64.p + 1);
+        u32* d_c0 = (u32*)(E.counters64.p + 1);
         static_assert(sizeof(seg_in) <= 12 * sizeof(u64), "entry slot");
-        seg_in* d_entry = (seg_in*)(counters64.p + 4);
+        seg_in* d_entry = (seg_in*)(E.counters64.p + 4);
         k_entry_seg<<<1, 1, 0, st>>>(S, a, entry.idxpos, entry.zmask, d_c0, d_entry);
-        // bitmaps: I (current speculation), I' (what the chain inserted), Ib (base set), scratch
-        u32* bmI = g_bmI.get(nw);
-        u32* bmI2 = g_bmI2.get(nw);
-        u32* bmIb = g_bmIb.get(nw);
-        u32* bmT = g_bmT.get(nw);
+        bmI = E.g_bmI.get(nw);
+        bmI2 = E.g_bmI2.get(nw);
+        bmIb = E.g_bmIb.get(nw);
+        bmT = E.g_bmT.get(nw);
         // the superset goes straight into Ib (the first base set); the scratch bitmap is
         // always fully overwritten before it is read
-        fills({{bmI, nw * 4, 0u}, {bmIb, nw * 4, 0u}});
+        E.fills({{bmI, nw * 4, 0u}, {bmIb, nw * 4, 0u}});
         if (nseg0)
             k_gap_bitmaps<<<capped_grid((u64)nseg0 * 64, 256), 256, 0, st>>>(S, nseg0, N, G.nt, hi_ins, off, bmI, bmIb);
         k_gap_bitmaps_phr<<<cdiv(m + 1, 256), 256, 0, st>>>(P, m, N, G.nt, a, hi_ins, off, bmI, bmIb);
         u32 hn[2];
-        u32 c0 = 0;
-        // the exact entry of the window as the completion path sees it
-        seg_in entry_in;
         {
             hread rb(st);
             rb.add(hn, S.nseg, 2);
@@ -2358,672 +2492,656 @@ u64 engine::factorize_greedy(const u8* T, u32 rk_seed, int log2_override, greedy
             rb.add(&entry_in, d_entry);
             rb.sync();
         }
-        const u32 nseg_init = hn[0];
-        lap("greedy setup");
+        nseg = hn[0];
+        C.lap(st, "greedy setup");
 
-        walk_ctx W{};
-        W.T = T;
+        W.T = C.T;
         W.G = G;
         W.P = P;
-        W.L = Lv;
+        W.L = C.Lv;
         W.bmoff = off;
-        W.Hs = Hs;
+        W.Hs = C.Hs;
         // speculative part: its bitmap of used entry-table slots; values below the
         // speculative block's start come from that table (earlier parts' writes do not)
-        W.hs_used = (blk && spec_track) ? g_hsused.p + (u64)spec_part * (spec_m / 32 + 1) : nullptr;
-        W.blk_start = blk ? (spec_track ? (pos_t)spec_base : blk->start) : 0;
+        W.hs_used = (C.blk && E.spec_track) ? E.g_hsused.p + (u64)E.spec_part * (E.spec_m / 32 + 1) : nullptr;
+        W.blk_start = C.blk ? (E.spec_track ? (pos_t)E.spec_base : C.blk->start) : 0;
+        W.use_pred = C.use_pred;
 
-        // window exit (the chain state at the first handover point >= bw) and the carried table
-        seg_in exit_in{};
-        // ---- bounded completion (k_seq_walk): the chain prefix [0, k*) is written by the
-        // segment walks, the rest of the window by the exact sequential walk from chain node k*
-        u64* d_sq = (u64*)g_cut.get(sizeof(chain_cut) + 256);
-        chain_cut* d_cutp = (chain_cut*)(d_sq + 8);
-        u64* d_y0 = d_sq + 6;
-        auto seq_complete = [&](const u32* chain, u32 nall, const u64* offs, const u32* ins_bm, bool from_entry) -> u64 {
-            if (from_entry) LZ_HIP(hipMemsetAsync(d_y0, 0, 8, st));
-            k_chain_cut<<<1, 1, 0, st>>>(S, chain, from_entry ? 0u : nall, d_y0, entry_in, d_cutp);
-            chain_cut cut;
-            {
-                hread rb(st);
-                rb.add(&cut, (const chain_cut*)d_cutp);
-                rb.sync();
-            }
-            const u64 offk = cut.k ? rd1(offs + cut.k, st) : 0;
-            pos_t* fo = fact.get(2 * (offk + (u64)(N - cut.in.start) + 2) + 2);
-            if (cut.k) {
-                k_walk<true><<<cdiv(cut.k, 64), 64, 0, st>>>(W, S, chain, cut.k, offs, fo);
-                LZ_HIP(hipGetLastError());
-            }
-            pos_t* H = g_H.get((u64)nslots_all);
-            if (Hs) LZ_HIP(hipMemcpyAsync(H, Hs, nslots_all * sizeof(pos_t), hipMemcpyDeviceToDevice, st));
-            else LZ_HIP(hipMemsetAsync(H, 0, nslots_all * sizeof(pos_t), st));
-            if (cut.in.start > off && ins_bm)
-                k_h_fill<<<cdiv(((u64)(cut.in.start - off) + 31) / 32, 256), 256, 0, st>>>(T, G, ins_bm, off, cut.in.start,
-                                                                                         H);
-            k_h_fix<<<cdiv(nslots_all, 256), 256, 0, st>>>(H, nslots_all);
-            k_seq_walk<<<1, 64, 0, st>>>(T, G, P, Lv, H, cut.in, last ? N + 1 : bw, fo, offk, d_sq, W.hs_used,
-                                         W.blk_start);
+        d_sq = (u64*)E.g_cut.get(sizeof(chain_cut) + 256);
+        d_cutp = (chain_cut*)(d_sq + 8);
+        d_y0 = d_sq + 6;
+        bmA = E.g_bmA.get(nw);
+        i_cnt = E.counters.get(16) + 12;
+        ids = E.g_ids.get(cap);
+        d_cnt = E.counters.get(16);
+        d_cs = (chain_status*)E.g_cs.get(sizeof(chain_status));
+    }
+
+    // ---- bounded completion (k_seq_walk): the chain prefix [0, k*) is written by the
+    // segment walks, the rest of the window by the exact sequential walk from chain node k*.
+    // Returns the window's factor count (0 with redo set: the hand-over point lies in the tail region)
+    u64 seq_complete(const u32* nodes, u32 nnodes, const u64* node_offs, const u32* ins_bm, bool from_entry) {
+        const pos_t N = C.N;
+        const gap_cfg& G = C.G;
+        const u64 nslots_all = C.nslots_all;
+        pos_t* const Hs = C.Hs;
+        if (from_entry) LZ_HIP(hipMemsetAsync(d_y0, 0, 8, st));
+        k_chain_cut<<<1, 1, 0, st>>>(S, nodes, from_entry ? 0u : nnodes, d_y0, entry_in, d_cutp);
+        chain_cut cut;
+        {
+            hread rb(st);
+            rb.add(&cut, (const chain_cut*)d_cutp);
+            rb.sync();
+        }
+        const u64 offk = cut.k ? rd1(node_offs + cut.k, st) : 0;
+        pos_t* fo = E.fact.get(2 * (offk + (u64)(N - cut.in.start) + 2) + 2);
+        if (cut.k) {
+            k_walk<true><<<cdiv(cut.k, 64), 64, 0, st>>>(W, S, nodes, cut.k, node_offs, fo);
             LZ_HIP(hipGetLastError());
-            u64 hc[4];
-            {
-                hread rb(st);
-                rb.add(hc, (const u64*)d_sq, 4);
-                rb.sync();
-            }
-            if (hc[1]) throw error(-6, "greedy: sequential completion guard tripped (internal error)");
-            if (!last && hc[2] >= (u64)G.nt) {
-                redo = true;  // the hand-over point lies in the tail region
-                return 0;
-            }
-            if (!last) {
-                exit_in.start = (pos_t)hc[2];
-                exit_in.idxpos = (pos_t)hc[3];
-                exit_in.zmask = 0;  // below the tail region no fingerprint is zeroed
-                k_h_unfix<<<cdiv(nslots_all, 256), 256, 0, st>>>(H, nslots_all, Hs);
-            }
-            stats[19] = 1;
-            stats[20] = cut.in.start;
-            lap("sequential completion");
-            return offk + hc[0];
-        };
+        }
+        pos_t* H = E.g_H.get((u64)nslots_all);
+        if (Hs) LZ_HIP(hipMemcpyAsync(H, Hs, nslots_all * sizeof(pos_t), hipMemcpyDeviceToDevice, st));
+        else LZ_HIP(hipMemsetAsync(H, 0, nslots_all * sizeof(pos_t), st));
+        if (cut.in.start > off && ins_bm)
+            k_h_fill<<<cdiv(((u64)(cut.in.start - off) + 31) / 32, 256), 256, 0, st>>>(C.T, G, ins_bm, off, cut.in.start, H);
+        k_h_fix<<<cdiv(nslots_all, 256), 256, 0, st>>>(H, nslots_all);
+        k_seq_walk<<<1, 64, 0, st>>>(C.T, G, C.P, C.Lv, H, cut.in, last ? N + 1 : bw, fo, offk, d_sq, W.hs_used,
+                                     W.blk_start);
+        LZ_HIP(hipGetLastError());
+        u64 hc[4];
+        {
+            hread rb(st);
+            rb.add(hc, (const u64*)d_sq, 4);
+            rb.sync();
+        }
+        if (hc[1]) throw error(-6, "greedy: sequential completion guard tripped (internal error)");
+        if (!last && hc[2] >= (u64)G.nt) {
+            redo = true;  // the hand-over point lies in the tail region
+            return 0;
+        }
+        if (!last) {
+            exit_in.start = (pos_t)hc[2];
+            exit_in.idxpos = (pos_t)hc[3];
+            exit_in.zmask = 0;  // below the tail region no fingerprint is zeroed
+            k_h_unfix<<<cdiv(nslots_all, 256), 256, 0, st>>>(H, nslots_all, Hs);
+        }
+        E.stats[19] = 1;
+        E.stats[20] = cut.in.start;
+        C.lap(st, "sequential completion");
+        return offk + hc[0];
+    }
 
-        // ---- base set (entries sorted by slot) and delta
-        u64 nb = 0;
-        const u32 nslots = G.mask + 1;
-        auto build_buckets = [&](auto key, u64 mk, dbuf<u32>& bk) {
-            u32* b = bk.get((u64)nslots + 1);
-            if (mk * 16 >= nslots) {
-                u32* rev = g_brev.get(2 * ((u64)nslots + 1));
-                u32* scn = rev + nslots + 1;
-                LZ_HIP(hipMemsetAsync(rev, 0xFF, ((u64)nslots + 1) * 4, st));
-                k_bucket_heads<<<cdiv(mk + 1, 256), 256, 0, st>>>(key, mk, nslots, rev);
+    // runs of a bitmap -> intervals (st, en), ranks, chunks for k_slots
+    ichunk* runs_to_chunks(const u32* bm, dbuf<pos_t>& dst, dbuf<pos_t>& den, dbuf<u32>& drk, dbuf<u8>& dch, u32& ni,
+                           u64& npos, u32& nch) {
+        const u64 tot = bmb_scan(bm_runs{bm}, nw, E.g_bsum, E.g_bincl, E.scan_tmp, st);
+        ni = (u32)(tot >> 32);  // run starts (= run ends)
+        pos_t* ra = dst.get(ni + 1);
+        pos_t* rb = den.get(ni + 1);
+        k_bmb_write<<<bmb_blocks, BMB_T, 0, st>>>(bm_runs{bm}, nw, E.g_bincl.p, out_runs{ra, rb}, off);
+        u32* len = E.g_tmp5.get(ni + 1);
+        u32* nc = E.g_tmp6.get(ni + 1);
+        u32* rk = drk.get(ni + 1);
+        u32* choff = E.g_tmp7.get(ni + 1);
+        npos = 0;
+        nch = 0;
+        u32 chl = SLOT_CHUNK_LONG;
+        if (ni) {
+            u32* ncs = E.g_tmp8.get(ni + 1);
+            const u32 scl = C.K.slot_chunk;
+            k_iv_chunk_counts<<<cdiv(ni, 256), 256, 0, st>>>(ra, rb, ni, nc, ncs, len, scl);
+            npos = excl_scan(len, rk, ni, E.scan_tmp, st);
+            if (npos < (u64)SLOT_CHUNK_LONG << C.K.slot_chunk_sh) chl = scl;
+            nch = excl_scan(chl == SLOT_CHUNK_LONG ? nc : ncs, choff, ni, E.scan_tmp, st);
+        }
+        ichunk* ch = (ichunk*)dch.get(std::max<u64>(1, nch) * sizeof(ichunk));
+        if (nch) k_iv_chunks<<<cdiv(nch, 256), 256, 0, st>>>(ra, rb, ni, choff, nch, chl, rk, ch);
+        return ch;
+    }
+
+    // debug: the base set's size and its first two intervals
+    void debug_base_dump(u32 ni, u32 nch) {
+        std::fprintf(stderr, "[lz77sss-debug] greedy base: intervals=%u positions=%llu chunks=%u slots=2^%u\n", ni,
+                     (unsigned long long)nb, nch, C.gp.log2_size_h);
+        pos_t r[4] = {0, 0, 0, 0};
+        if (ni) {
+            LZ_HIP(hipMemcpy(r, E.ist.p, sizeof(pos_t) * std::min<u32>(ni, 2), hipMemcpyDeviceToHost));
+            LZ_HIP(hipMemcpy(r + 2, E.iend.p, sizeof(pos_t) * std::min<u32>(ni, 2), hipMemcpyDeviceToHost));
+        }
+        std::fprintf(stderr, "[lz77sss-debug] greedy base: window [%llu, %llu) off=%llu nw=%llu runs %llu-%llu %llu-%llu\n",
+                     (unsigned long long)a, (unsigned long long)bw, (unsigned long long)off, (unsigned long long)nw,
+                     (unsigned long long)r[0], (unsigned long long)r[2], (unsigned long long)r[1], (unsigned long long)r[3]);
+    }
+
+    // ---- the base set of the positions in bm: entries sorted by slot, predecessors or buckets.
+    // Base sets of pred_sorted_min entries or more get their predecessors in sorted order and moved
+    // back to entry order in buckets (random 4-byte scatters over the whole array are slower)
+    void build_base(const u32* bm) {
+        const greedy_knobs& K = C.K;
+        const gap_params_h& gp = C.gp;
+        if (bm != bmIb) LZ_HIP(hipMemcpyAsync(bmIb, bm, nw * 4, hipMemcpyDeviceToDevice, st));
+        u32 ni, nch;
+        ichunk* ch = runs_to_chunks(bmIb, E.ist, E.iend, E.irank, E.chunk_buf, ni, nb, nch);
+        if (C.dbg) debug_base_dump(ni, nch);
+        C.lap(st, "base intervals");
+        if (5 * nb >= (1ull << 32))
+            throw error(-1, "gap region of a greedy window too large for 32-bit entry ids (set LZ77SSS_GREEDY_WINDOW)");
+        const u64 ne5 = 5 * nb;
+        u32* keys = E.ekeys.get(ne5 + 1);
+        u32* vals = E.evals.get(ne5 + 1);
+        u32* skeys = E.ekeys2.get(ne5 + 1);
+        u32* svals = E.evals2.get(ne5 + 1);
+        pos_t* ipos = E.ipos_buf.get(nb + 1);
+        u32* pred5 = E.occ_buf.get(ne5 + 1);
+        u8* rem = E.rem_buf.get(nb + 1);
+        bool dense = false, ls = false;
+        u32 D = 0, dense_bits = 0;
+        const u64 npw = ((u64)nslots + 31) / 32;
+        u32* pbm = E.g_pbm.get(npw + 1);
+        u32* pwp = E.g_pwp.get(npw + 1);
+        // distinct slots -> dense ids when that saves radix passes (tried below 2^28 entries:
+        // a base set that large comes from a non-repetitive text, whose slots are all in use);
+        // k_slots marks the present slots
+        const bool try_dense = nch && ne5 < (1ull << 28) && !K.no_dense;
+        u8* pf = try_dense ? (u8*)E.g_pflag.get(npw * 8) : nullptr;
+        E.fills({{rem, nb + 1, 0u}, {pf, pf ? npw * 32 : 0, 0u}});
+        if (nch) {
+            k_slots<<<cdiv(nch, SL_CH), SL_T, 0, st>>>(C.T, C.G, ch, nch, keys, nullptr, ipos, pf);
+            C.lap(st, "base slots");
+            if (try_dense) {
+                u32* pcnt = E.g_pcnt.get(npw + 1);
+                k_presence_pack<<<cdiv(npw, 256), 256, 0, st>>>(pf, npw, pbm, pcnt);
+                D = excl_scan(pcnt, pwp, npw, E.scan_tmp, st);
+                u32 dbits = 1;
+                while (dbits < 32 && (1ull << dbits) < D) dbits++;
+                dense = (dbits + 7) / 8 < (gp.log2_size_h + 7) / 8;
+                dense_bits = dbits;
+            }
+            u32* sk_in = keys;
+            u32 sbits = gp.log2_size_h;
+            // dense ids and bucket-search lookups (no predecessors): the LSD sort over the raw
+            // slots, dense-id map fused into its first pass, entry ids and dense-id starts out
+            ls = dense && !W.use_pred && !K.no_lsd;
+            if (ls) {
+                u32* dstart = E.g_dstart.get((u64)D + 2);
+                E.fills({{dstart, (u64)D * 4, ~0u}, {dstart + D, 4, (u32)ne5}, {dstart + D + 1, 4, 0u}});
+                u64* pbw = (u64*)E.g_pbw.get(2 * npw);
+                k_pack_pbw<<<cdiv(npw, 256), 256, 0, st>>>(pbm, pwp, npw, pbw);
+                lsd_sort(E, K, ls_dense{keys, pbw}, ne5, dense_bits, skeys, vals, svals, dstart, D);
+                if (K.lsd_check) lsd_check(E, keys, ne5, pbm, pwp, npw, D, dense_bits, svals, dstart);
+                if (C.dbg)
+                    std::fprintf(stderr, "[lz77sss-debug] greedy base: %u distinct slots, LSD sort on %u bits\n", D,
+                                 dense_bits);
+            } else if (dense) {
+                // (a transform iterator mapping the ids inside the sort was slower: rr sort
+                // passes +234 us against this pass's 211 us)
+                k_dense_keys<<<cdiv(cdiv(ne5, 4), 256), 256, 0, st>>>(keys, ne5, pbm, pwp, skeys);
+                sk_in = skeys;
+                skeys = E.g_sdk.get(ne5 + 1);
+                sbits = dense_bits;
+            }
+            if (!ls) {
+                if (C.dbg)
+                    std::fprintf(stderr, "[lz77sss-debug] greedy base: %u distinct slots, %s sort on %u bits\n", D,
+                                 dense ? "dense-id" : "slot", sbits);
                 size_t tb = 0;
-                LZ_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, tb, rev, scn, min_u32_op{}, (int)(nslots + 1), st));
-                u8* t = scan_tmp.get(tb);
-                LZ_HIP(hipcub::DeviceScan::InclusiveScan(t, tb, rev, scn, min_u32_op{}, (int)(nslots + 1), st));
-                k_unreverse<<<cdiv((u64)nslots + 1, 256), 256, 0, st>>>(scn, nslots, b);
-            } else {
-                k_bucket_search<<<cdiv((u64)nslots + 1, 256), 256, 0, st>>>(key, mk, nslots, b);
-            }
-        };
-        // runs of a bitmap -> intervals (st, en), ranks, chunks for k_slots
-        auto runs_to_chunks = [&](const u32* bm, dbuf<pos_t>& dst, dbuf<pos_t>& den, dbuf<u32>& drk, dbuf<u8>& dch,
-                                  u32& ni, u64& npos, u32& nch) -> ichunk* {
-            const u64 tot = bmb_scan(bm_runs{bm}, nw, g_bsum, g_bincl, scan_tmp, st);
-            ni = (u32)(tot >> 32);  // run starts (= run ends)
-            pos_t* ra = dst.get(ni + 1);
-            pos_t* rb = den.get(ni + 1);
-            k_bmb_write<<<bmb_blocks, BMB_T, 0, st>>>(bm_runs{bm}, nw, g_bincl.p, out_runs{ra, rb}, off);
-            u32* len = g_tmp5.get(ni + 1);
-            u32* nc = g_tmp6.get(ni + 1);
-            u32* rk = drk.get(ni + 1);
-            u32* choff = g_tmp7.get(ni + 1);
-            npos = 0;
-            nch = 0;
-            u32 chl = SLOT_CHUNK_LONG;
-            if (ni) {
-                u32* ncs = g_tmp8.get(ni + 1);
-                // short chunks (test/tuning knob LZ77SSS_SLOT_CHUNK, <= SLOT_CHUNK_LONG)
-                const char* sce = std::getenv("LZ77SSS_SLOT_CHUNK");
-                const u32 scl = sce ? std::max(8u, std::min<u32>(SLOT_CHUNK_LONG, (u32)std::atoi(sce))) : SLOT_CHUNK_SHORT;
-                k_iv_chunk_counts<<<cdiv(ni, 256), 256, 0, st>>>(ra, rb, ni, nc, ncs, len, scl);
-                npos = excl_scan(len, rk, ni, scan_tmp, st);
-                if (npos < (u64)SLOT_CHUNK_LONG << (std::getenv("LZ77SSS_SLOT_CHUNK_SH") ? std::atoi(std::getenv("LZ77SSS_SLOT_CHUNK_SH")) : 18)) chl = scl;
-                nch = excl_scan(chl == SLOT_CHUNK_LONG ? nc : ncs, choff, ni, scan_tmp, st);
-            }
-            ichunk* ch = (ichunk*)dch.get(std::max<u64>(1, nch) * sizeof(ichunk));
-            if (nch) k_iv_chunks<<<cdiv(nch, 256), 256, 0, st>>>(ra, rb, ni, choff, nch, chl, rk, ch);
-            return ch;
-        };
-        // LSD sort of m entries on `bits` key bits (pass-0 keys from kf0): entry ids to vout, the first
-        // sorted index of every key to head (pre-set to NONE); ka / va: scratch for the middle passes
-        auto lsd_sort = [&](auto kf0, u64 m, u32 bits, u32* ka, u32* va, u32* vout, u32* head, u32 nkeys) {
-            const u32 npass = std::max<u32>(1, (bits + LS_DB - 1) / LS_DB);
-            if (npass > LS_MAXP) throw error(-6, "lsd_sort: too many key bits");
-            const u32 ntile = cdiv(m, LS_TILE);
-            const u64 per = (u64)LS_NB * ntile;
-            u32* H = g_ls_h.get(per + 1);
-            u32* Gs = g_ls_g.get(per + 1);
-            // the first pass (entry order: many distinct digits per wave) block-sorts its tiles, the
-            // later ones (inputs sorted on the lower digits: few per wave) rank by ballots
-            // (rr 13-bit dense keys: pass 0 278 vs 369 us, pass 1 167 vs 284 us); LZ77SSS_LS_BLOCKSORT /
-            // LZ77SSS_LS_RANK force either for every pass
-            const bool all_bs = std::getenv("LZ77SSS_LS_BLOCKSORT") != nullptr, all_rk = std::getenv("LZ77SSS_LS_RANK") != nullptr;
-            auto use_bsort = [&](u32 p) { return all_bs || (!all_rk && p == 0); };
-            const bool bsort = use_bsort(npass - 1);  // the last pass: heads in the block-sort kernel
-            // ping-pong: pass p reads what pass p - 1 wrote (the ranking form writes the last pass's
-            // keys too, for the key heads)
-            const bool kb1 = npass > 2 || (head && !bsort && npass > 1);
-            u32 *kb[2] = {ka, kb1 ? g_predk.get(m + 1) : nullptr}, *vb[2] = {va, npass > 2 ? g_ids2.get(m + 1) : nullptr};
-            u32* klast = nullptr;
-            for (u32 p = 0; p < npass; p++) {
-                const bool first = p == 0, lastp = p + 1 == npass;
-                u32 *ko = kb[p & 1], *vo = lastp ? vout : vb[p & 1];
-                const u32 *ki = kb[(p + 1) & 1], *vi = vb[(p + 1) & 1];
-                const ls_plain kp{ki};
-                if (first) k_ls_hist<decltype(kf0), false><<<ntile, LS_T, 0, st>>>(kf0, m, p, ntile, H);
-                else k_ls_hist<ls_plain, true><<<ntile, LS_T, 0, st>>>(kp, m, p, ntile, H);
-                excl_sum64(H, Gs, 0u, per, scan_tmp, st);
-                if (use_bsort(p)) {
-                    if (first && lastp)
-                        k_ls_scatter<decltype(kf0), true, true><<<ntile, LS_T, 0, st>>>(kf0, ki, vi, m, p, ntile, Gs, ko, vo, head);
-                    else if (first)
-                        k_ls_scatter<decltype(kf0), true, false><<<ntile, LS_T, 0, st>>>(kf0, ki, vi, m, p, ntile, Gs, ko, vo, head);
-                    else if (lastp)
-                        k_ls_scatter<ls_plain, false, true><<<ntile, LS_T, 0, st>>>(kp, ki, vi, m, p, ntile, Gs, ko, vo, head);
-                    else
-                        k_ls_scatter<ls_plain, false, false><<<ntile, LS_T, 0, st>>>(kp, ki, vi, m, p, ntile, Gs, ko, vo, head);
-                } else {
-                    u32* kw = (lastp && !head) ? nullptr : ko;
-                    if (lastp) klast = kw;
-                    if (first && lastp)
-                        k_ls_rank<decltype(kf0), true, true><<<ntile, LS_T, 0, st>>>(kf0, ki, vi, m, p, ntile, Gs, kw, vo);
-                    else if (first)
-                        k_ls_rank<decltype(kf0), true, false><<<ntile, LS_T, 0, st>>>(kf0, ki, vi, m, p, ntile, Gs, kw, vo);
-                    else if (lastp)
-                        k_ls_rank<ls_plain, false, true><<<ntile, LS_T, 0, st>>>(kp, ki, vi, m, p, ntile, Gs, kw, vo);
-                    else
-                        k_ls_rank<ls_plain, false, false><<<ntile, LS_T, 0, st>>>(kp, ki, vi, m, p, ntile, Gs, kw, vo);
-                }
-            }
-            if (head && !bsort) k_dense_heads<<<cdiv(cdiv(m + 1, 4), 256), 256, 0, st>>>(klast, m, nkeys, head);
-            LZ_HIP(hipGetLastError());
-        };
-        // base sets this large get their predecessors in sorted order and moved back to
-        // entry order in buckets (random 4-byte scatters over the whole array are slower)
-        auto build_base = [&](const u32* bm) {
-            if (bm != bmIb) LZ_HIP(hipMemcpyAsync(bmIb, bm, nw * 4, hipMemcpyDeviceToDevice, st));
-            u32 ni, nch;
-            ichunk* ch = runs_to_chunks(bmIb, ist, iend, irank, chunk_buf, ni, nb, nch);
-            if (dbg) {
-                std::fprintf(stderr, "[lz77sss-debug] greedy base: intervals=%u positions=%llu chunks=%u slots=2^%u\n", ni,
-                             (unsigned long long)nb, nch, gp.log2_size_h);
-                pos_t r[4] = {0, 0, 0, 0};
-                if (ni) {
-                    LZ_HIP(hipMemcpy(r, ist.p, sizeof(pos_t) * std::min<u32>(ni, 2), hipMemcpyDeviceToHost));
-                    LZ_HIP(hipMemcpy(r + 2, iend.p, sizeof(pos_t) * std::min<u32>(ni, 2), hipMemcpyDeviceToHost));
-                }
-                std::fprintf(stderr, "[lz77sss-debug] greedy base: window [%llu, %llu) off=%llu nw=%llu runs %llu-%llu %llu-%llu\n",
-                             (unsigned long long)a, (unsigned long long)bw, (unsigned long long)off,
-                             (unsigned long long)nw, (unsigned long long)r[0], (unsigned long long)r[2],
-                             (unsigned long long)r[1], (unsigned long long)r[3]);
-            }
-            lap("base intervals");
-            if (5 * nb >= (1ull << 32))
-                throw error(-1, "gap region of a greedy window too large for 32-bit entry ids (set LZ77SSS_GREEDY_WINDOW)");
-            const u64 ne5 = 5 * nb;
-            u32* keys = ekeys.get(ne5 + 1);
-            u32* vals = evals.get(ne5 + 1);
-            u32* skeys = ekeys2.get(ne5 + 1);
-            u32* svals = evals2.get(ne5 + 1);
-            pos_t* ipos = ipos_buf.get(nb + 1);
-            u32* pred5 = occ_buf.get(ne5 + 1);
-            u8* rem = rem_buf.get(nb + 1);
-            bool dense = false, ls = false;
-            u32 D = 0, dense_bits = 0;
-            const u64 npw = ((u64)nslots + 31) / 32;
-            u32* pbm = g_pbm.get(npw + 1);
-            u32* pwp = g_pwp.get(npw + 1);
-            // distinct slots -> dense ids when that saves radix passes (tried below 2^28 entries:
-            // a base set that large comes from a non-repetitive text, whose slots are all in use);
-            // k_slots marks the present slots
-            const bool try_dense = nch && ne5 < (1ull << 28) && !std::getenv("LZ77SSS_NO_DENSE");
-            u8* pf = try_dense ? (u8*)g_pflag.get(npw * 8) : nullptr;
-            fills({{rem, nb + 1, 0u}, {pf, pf ? npw * 32 : 0, 0u}});
-            if (nch) {
-                k_slots<<<cdiv(nch, SL_CH), SL_T, 0, st>>>(T, G, ch, nch, keys, nullptr, ipos, pf);
-                lap("base slots");
-                if (try_dense) {
-                    u32* pcnt = g_pcnt.get(npw + 1);
-                    k_presence_pack<<<cdiv(npw, 256), 256, 0, st>>>(pf, npw, pbm, pcnt);
-                    D = excl_scan(pcnt, pwp, npw, scan_tmp, st);
-                    u32 dbits = 1;
-                    while (dbits < 32 && (1ull << dbits) < D) dbits++;
-                    dense = (dbits + 7) / 8 < (gp.log2_size_h + 7) / 8;
-                    dense_bits = dbits;
-                }
-                u32* sk_in = keys;
-                u32 sbits = gp.log2_size_h;
-                // dense ids and bucket-search lookups (no predecessors): the LSD sort over the raw
-                // slots, dense-id map fused into its first pass, entry ids and dense-id starts out
-                ls = dense && !W.use_pred && !std::getenv("LZ77SSS_NO_LSD");
-                if (ls) {
-                    u32* dstart = g_dstart.get((u64)D + 2);
-                    fills({{dstart, (u64)D * 4, ~0u}, {dstart + D, 4, (u32)ne5}, {dstart + D + 1, 4, 0u}});
-                    u64* pbw = (u64*)g_pbw.get(2 * npw);
-                    k_pack_pbw<<<cdiv(npw, 256), 256, 0, st>>>(pbm, pwp, npw, pbw);
-                    lsd_sort(ls_dense{keys, pbw}, ne5, dense_bits, skeys, vals, svals, dstart, D);
-                    if (std::getenv("LZ77SSS_LSD_CHECK")) {
-                        // the rocprim path into scratch, compared entry by entry
-                        u32* dk = g_sdk.get(ne5 + 1);
-                        u32* ck = g_predk.get(ne5 + 1);
-                        u32* cv = g_ids2.get(ne5 + 1);
-                        k_dense_keys<<<cdiv(cdiv(ne5, 4), 256), 256, 0, st>>>(keys, ne5, pbm, pwp, dk);
-                        size_t tb = 0;
-                        const rocprim::counting_iterator<u32> ids(0);
-                        LZ_HIP(rocprim::radix_sort_pairs(nullptr, tb, dk, ck, ids, cv, (size_t)ne5, 0u, dense_bits, st));
-                        u8* t = scan_tmp.get(tb);
-                        LZ_HIP(rocprim::radix_sort_pairs(t, tb, dk, ck, ids, cv, (size_t)ne5, 0u, dense_bits, st));
-                        u32* ds2 = g_pcnt.get(std::max<u64>(npw + 1, (u64)D + 2));
-                        k_pred_heads<<<cdiv(ne5 + 1, 256), 256, 0, st>>>(ck, cv, ne5, D, nullptr, ds2);
-                        u64* r = (u64*)g_cut.get(sizeof(chain_cut) + 256) + 20;
-                        const u64 init[4] = {~0ull, 0, ~0ull, 0};
-                        LZ_HIP(hipMemcpyAsync(r, init, 32, hipMemcpyHostToDevice, st));
-                        k_first_diff_u32<<<cdiv(ne5, 256), 256, 0, st>>>(svals, cv, ne5, r);
-                        k_first_diff_u32<<<cdiv((u64)D + 1, 256), 256, 0, st>>>(dstart, ds2, (u64)D + 1, r + 2);
-                        u64 h[4];
-                        LZ_HIP(hipMemcpyAsync(h, r, 32, hipMemcpyDeviceToHost, st));
-                        LZ_HIP(hipStreamSynchronize(st));
-                        std::fprintf(stderr, "[lz77sss-lsd-check] m=%llu D=%u bits=%u: svals diff=%llu first=%lld, dstart diff=%llu first=%lld\n",
-                                     (unsigned long long)ne5, D, dense_bits, (unsigned long long)h[1], (long long)h[0],
-                                     (unsigned long long)h[3], (long long)h[2]);
-                        if (h[1] || h[3]) {
-                            u32 a[8], b[8];
-                            const u64 f = h[1] ? std::min<u64>(h[0], ne5 - 8) : 0;
-                            LZ_HIP(hipMemcpy(a, svals + f, 32, hipMemcpyDeviceToHost));
-                            LZ_HIP(hipMemcpy(b, cv + f, 32, hipMemcpyDeviceToHost));
-                            for (int q = 0; q < 8; q++) std::fprintf(stderr, "  [%llu] lsd %u rocprim %u\n", (unsigned long long)(f + q), a[q], b[q]);
-                        }
-                    }
-                    if (dbg)
-                        std::fprintf(stderr, "[lz77sss-debug] greedy base: %u distinct slots, LSD sort on %u bits\n", D,
-                                     dense_bits);
-                } else if (dense) {
-                    // (a transform iterator mapping the ids inside the sort was slower: rr sort
-                    // passes +234 us against this pass's 211 us)
-                    k_dense_keys<<<cdiv(cdiv(ne5, 4), 256), 256, 0, st>>>(keys, ne5, pbm, pwp, skeys);
-                    sk_in = skeys;
-                    skeys = g_sdk.get(ne5 + 1);
-                    sbits = dense_bits;
-                }
-                if (!ls) {
-                    if (dbg)
-                        std::fprintf(stderr, "[lz77sss-debug] greedy base: %u distinct slots, %s sort on %u bits\n", D,
-                                     dense ? "dense-id" : "slot", sbits);
-                    size_t tb = 0;
-                    // values = entry ids: a counting iterator, so the ids are never written or read
-                    const rocprim::counting_iterator<u32> ids(0);
-                    LZ_HIP(rocprim::radix_sort_pairs(nullptr, tb, sk_in, skeys, ids, svals, (size_t)ne5, 0u, sbits, st));
-                    u8* t = scan_tmp.get(tb);
-                    LZ_HIP(rocprim::radix_sort_pairs(t, tb, sk_in, skeys, ids, svals, (size_t)ne5, 0u, sbits, st));
-                    if (dense && ne5 < pred_sorted_min) {
-                        // predecessors and dense-id starts in one pass (buckets below reuse dstart)
-                        k_pred_heads<<<cdiv(ne5 + 1, 256), 256, 0, st>>>(skeys, svals, ne5, D, W.use_pred ? pred5 : nullptr,
-                                                                          g_dstart.get((u64)D + 1));
-                    } else if (W.use_pred && ne5 < pred_sorted_min) {
-                        k_pred<<<cdiv(ne5, 256), 256, 0, st>>>(skeys, svals, ne5, pred5);
-                    } else if (W.use_pred) {
-                        // pred5[e] = predecessor of entry e in its slot: the sorted-order predecessors
-                        // moved back to entry order (a random scatter of 4-byte writes is ~3x slower)
-                        if (std::getenv("LZ77SSS_PRED_RADIX")) {  // reference path: radix sort by entry id
-                            u32* pv = vals;  // the unsorted values are no longer needed
-                            k_pred_sorted<<<cdiv(ne5, 256), 256, 0, st>>>(skeys, svals, ne5, pv);
-                            u32* kdump = g_predk.get(ne5 + 1);
-                            int eb = 1;
-                            while (eb < 32 && (1ull << eb) < ne5) eb++;
-                            size_t tb2 = 0;
-                            LZ_HIP(rocprim::radix_sort_pairs(nullptr, tb2, svals, kdump, pv, pred5, (size_t)ne5, 0u,
-                                                             (unsigned)eb, st));
-                            u8* t2 = scan_tmp.get(tb2);
-                            LZ_HIP(rocprim::radix_sort_pairs(t2, tb2, svals, kdump, pv, pred5, (size_t)ne5, 0u, (unsigned)eb,
-                                                             st));
-                        } else {
-                            const u32 nbk = (u32)((ne5 + (1ull << PB_SH) - 1) >> PB_SH);
-                            u32* cursor = g_pbcur.get(nbk + 1);
-                            u64* tmp = g_pbtmp.get(ne5);
-                            const u32 ntile = (u32)std::min<u64>(1024, cdiv(ne5, PB_T));
-                            const u64 tile = (ne5 + ntile - 1) / ntile;
-                            k_pb_init<<<cdiv(nbk, 256), 256, 0, st>>>(cursor, nbk);
-                            k_pb_move<<<ntile, PB_T, 0, st>>>(svals, skeys, ne5, tile, nbk, cursor, tmp);
-                            k_pb_apply<<<cdiv(cdiv(ne5, 256), N_XCD) * N_XCD, 256, 0, st>>>(tmp, ne5, pred5);
-                        }
+                // values = entry ids: a counting iterator, so the ids are never written or read
+                const rocprim::counting_iterator<u32> cids(0);
+                LZ_HIP(rocprim::radix_sort_pairs(nullptr, tb, sk_in, skeys, cids, svals, (size_t)ne5, 0u, sbits, st));
+                u8* t = E.scan_tmp.get(tb);
+                LZ_HIP(rocprim::radix_sort_pairs(t, tb, sk_in, skeys, cids, svals, (size_t)ne5, 0u, sbits, st));
+                if (dense && ne5 < K.pred_sorted_min) {
+                    // predecessors and dense-id starts in one pass (buckets below reuse dstart)
+                    k_pred_heads<<<cdiv(ne5 + 1, 256), 256, 0, st>>>(skeys, svals, ne5, D, W.use_pred ? pred5 : nullptr,
+                                                                      E.g_dstart.get((u64)D + 1));
+                } else if (W.use_pred && ne5 < K.pred_sorted_min) {
+                    k_pred<<<cdiv(ne5, 256), 256, 0, st>>>(skeys, svals, ne5, pred5);
+                } else if (W.use_pred) {
+                    // pred5[e] = predecessor of entry e in its slot: the sorted-order predecessors
+                    // moved back to entry order (a random scatter of 4-byte writes is ~3x slower)
+                    if (K.pred_radix) {  // reference path: radix sort by entry id
+                        u32* pv = vals;  // the unsorted values are no longer needed
+                        k_pred_sorted<<<cdiv(ne5, 256), 256, 0, st>>>(skeys, svals, ne5, pv);
+                        u32* kdump = E.g_predk.get(ne5 + 1);
+                        int eb = 1;
+                        while (eb < 32 && (1ull << eb) < ne5) eb++;
+                        size_t tb2 = 0;
+                        LZ_HIP(rocprim::radix_sort_pairs(nullptr, tb2, svals, kdump, pv, pred5, (size_t)ne5, 0u,
+                                                         (unsigned)eb, st));
+                        u8* t2 = E.scan_tmp.get(tb2);
+                        LZ_HIP(rocprim::radix_sort_pairs(t2, tb2, svals, kdump, pv, pred5, (size_t)ne5, 0u, (unsigned)eb,
+                                                         st));
+                    } else {
+                        const u32 nbk = (u32)((ne5 + (1ull << PB_SH) - 1) >> PB_SH);
+                        u32* cursor = E.g_pbcur.get(nbk + 1);
+                        u64* tmp = E.g_pbtmp.get(ne5);
+                        const u32 ntile = (u32)std::min<u64>(1024, cdiv(ne5, PB_T));
+                        const u64 tile = (ne5 + ntile - 1) / ntile;
+                        k_pb_init<<<cdiv(nbk, 256), 256, 0, st>>>(cursor, nbk);
+                        k_pb_move<<<ntile, PB_T, 0, st>>>(svals, skeys, ne5, tile, nbk, cursor, tmp);
+                        k_pb_apply<<<cdiv(cdiv(ne5, 256), N_XCD) * N_XCD, 256, 0, st>>>(tmp, ne5, pred5);
                     }
                 }
             }
-            lap("base sort + pred");
-            if (dense) {
-                u32* dstart = g_dstart.get((u64)D + 1);
-                if (ne5 >= pred_sorted_min && !ls)
-                    k_dense_heads<<<cdiv(cdiv(ne5 + 1, 4), 256), 256, 0, st>>>(skeys, ne5, D, dstart);
-                k_bstart_rank<<<cdiv(cdiv((u64)nslots + 1, 4), 256), 256, 0, st>>>(pbm, pwp, dstart, nslots, D,
-                                                                          g_bstart.get((u64)nslots + 1));
-            } else {
-                build_buckets(key_u32{skeys}, ne5, g_bstart);
-            }
-            W.istart = ist.p; W.iend = iend.p; W.irank = irank.p; W.nint = ni;
-            W.keys = keys; W.skeys = skeys; W.svals = svals; W.pred5 = pred5; W.ipos = ipos; W.nentries = ne5;
-            W.bstart = g_bstart.p;
-            W.rem = rem; W.akeys = nullptr; W.nadd = 0; W.akeys2 = nullptr; W.nadd2 = 0;
-            // removed flags packed into the positions (the flag bit is above every position)
-            W.iposr = (W.use_pred && (u64)N < (u64)POS_RFLAG && !std::getenv("LZ77SSS_NO_IPOSR"))
-                          ? iposr_buf.get(nb + 1) : nullptr;
-            lap("base buckets");
-        };
-        // added entries: positions of I outside the base set.  The main list is
-        // rebuilt rarely (membership of its positions is read from the I bitmap);
-        // positions that join later and are missing from it go to the small extra list.
-        u32* bmA = g_bmA.get(nw);
-        u64 na_main = 0;
-        bool bmA_zero = false;  // the main list is empty and bmA was not computed (I within the base set)
-        // I_fresh: I was set by set_state(true) and not changed since (I lies within the base set), so
-        // I' == I is decided by two checks over the chain's inserts and the base ranks (i_cnt[0]:
-        // inserts outside I, i_cnt[1]: positions of I not inserted) instead of a full-length xor and count
-        bool I_fresh = false;
-        u32* i_cnt = counters.get(16) + 12;
-        auto build_list = [&](const u32* bm, dbuf<u32>& k32, dbuf<pos_t>& kpos, dbuf<u64>& ka, dbuf<u64>& kb,
-                              dbuf<u32>& bucket, const u64*& keys_out, u64& nkeys, const u32*& bk_out,
-                              const pos_t*& apos_out, u64& napos_out) -> u64 {
-            u32 ni, nch;
-            u64 na;
-            ichunk* ch = runs_to_chunks(bm, g_ast, g_aen, g_ark, chunk_buf2, ni, na, nch);
-            nkeys = 0;
-            keys_out = nullptr;
-            apos_out = nullptr;
-            napos_out = 0;
-            if (!na) return 0;
-            u32* akey32 = k32.get(5 * na);
-            pos_t* apos = kpos.get(na);
-            apos_out = apos;
-            napos_out = na;
-            k_slots<<<cdiv(nch, SL_CH), SL_T, 0, st>>>(T, G, ch, nch, akey32, nullptr, apos);
-            u64* ak = ka.get(5 * na);
-            u64* ak2 = kb.get(5 * na);
-            k_pack_added<<<cdiv(5 * na, 256), 256, 0, st>>>(akey32, apos, 5 * na, ak);
-            size_t tb = 0;
-            LZ_HIP(rocprim::radix_sort_keys(nullptr, tb, ak, ak2, (size_t)(5 * na), 0u, 63u, st));
-            u8* t = scan_tmp.get(tb);
-            LZ_HIP(rocprim::radix_sort_keys(t, tb, ak, ak2, (size_t)(5 * na), 0u, 63u, st));
-            keys_out = ak2;
-            nkeys = 5 * na;
-            build_buckets(key_u64{ak2}, 5 * na, bucket);
-            bk_out = bucket.p;
-            return na;
-        };
-        auto rebuild_main = [&]() {
-            bmA_zero = false;
-            k_bm_andnot<<<gw, 256, 0, st>>>(bmI, bmIb, nw, bmA);
-            na_main = build_list(bmA, add_keys32, add_pos, add_keys, add_keys2, g_abeg, W.akeys, W.nadd, W.abeg, W.apos,
-                                 W.napos);
-            W.nadd2 = 0;
-            W.akeys2 = nullptr;
-        };
-        auto rebuild_added = [&](bool main_list) {
-            if (main_list) return rebuild_main();
-            k_bm_andnot<<<gw, 256, 0, st>>>(bmI, bmIb, nw, bmT);
-            if (!bmA_zero) k_bm_andnot<<<gw, 256, 0, st>>>(bmT, bmA, nw, bmT);
-            const u64 nx = build_list(bmT, g_x32, g_xpos, g_xk, g_xk2, g_abeg2, W.akeys2, W.nadd2, W.abeg2, W.apos2,
-                                      W.napos2);
-            if (nx * 4 > na_main + (1u << 16)) rebuild_main();
-        };
-        // rem + added for the current I; within_base: I is a subset of the base set (the first
-        // speculation, or a base rebuilt as I' u I_b), so no position is added and the main list
-        // (I - I_b, a full-length bitmap pass and a count) is empty without computing it
-        auto set_state = [&](bool within_base) {
-            W.bmI = bmI;
-            I_fresh = within_base;
-            if (nb)
-                k_rem_from_bm<<<cdiv(nb, 256), 256, 0, st>>>(W.ipos, nb, bmI, off, (u8*)W.rem, (pos_t*)W.iposr);
-            if (!within_base) return rebuild_added(true);
-            bmA_zero = true;
-            na_main = 0;
-            W.akeys = nullptr; W.nadd = 0; W.abeg = nullptr; W.apos = nullptr; W.napos = 0;
-            W.akeys2 = nullptr; W.nadd2 = 0;
-        };
-        // same-slot predecessors (pred5) pay for their scatter when the walks make many
-        // lookups: short gaps (many factors per gap position).  Texts with few, long gaps
-        // (long factors, few lookups) search the buckets instead.  LZ77SSS_PRED /
-        // LZ77SSS_NO_PRED force either path (tests).
-        W.use_pred = std::getenv("LZ77SSS_PRED") ? 1
-                     : std::getenv("LZ77SSS_NO_PRED") ? 0
-                     : ((u64)(N - len_lpf_phr) < 4096ull * (u64)std::max<u64>(1, num_gaps)) ? 1 : 0;
+        }
+        C.lap(st, "base sort + pred");
+        if (dense) {
+            u32* dstart = E.g_dstart.get((u64)D + 1);
+            if (ne5 >= K.pred_sorted_min && !ls)
+                k_dense_heads<<<cdiv(cdiv(ne5 + 1, 4), 256), 256, 0, st>>>(skeys, ne5, D, dstart);
+            k_bstart_rank<<<cdiv(cdiv((u64)nslots + 1, 4), 256), 256, 0, st>>>(pbm, pwp, dstart, nslots, D,
+                                                                      E.g_bstart.get((u64)nslots + 1));
+        } else {
+            build_buckets(E, nslots, key_u32{skeys}, ne5, E.g_bstart);
+        }
+        W.istart = E.ist.p; W.iend = E.iend.p; W.irank = E.irank.p; W.nint = ni;
+        W.keys = keys; W.skeys = skeys; W.svals = svals; W.pred5 = pred5; W.ipos = ipos; W.nentries = ne5;
+        W.bstart = E.g_bstart.p;
+        W.rem = rem; W.akeys = nullptr; W.nadd = 0; W.akeys2 = nullptr; W.nadd2 = 0;
+        // removed flags packed into the positions (the flag bit is above every position)
+        W.iposr = (W.use_pred && (u64)C.N < (u64)POS_RFLAG && !K.no_iposr) ? E.iposr_buf.get(nb + 1) : nullptr;
+        C.lap(st, "base buckets");
+    }
 
-        // ---- walk + link until the chain from the window entry is complete, then check I
-        u32 nseg = nseg_init;
-        u32* ids = g_ids.get(cap);
-        u32* d_cnt = counters.get(16);
-        chain_status cs{};
-        chain_status* d_cs = (chain_status*)g_cs.get(sizeof(chain_status));
-        jump_levels JL{};
-        u64 wfact = 0, walked_total = 0;
-        int outer = 0, rounds_total = 0;
+    // added entries: the positions of bm (a part of I outside the base set) as a list sorted by
+    // slot with its buckets; returns their number
+    u64 build_list(const u32* bm, dbuf<u32>& k32, dbuf<pos_t>& kpos, dbuf<u64>& ka, dbuf<u64>& kb, dbuf<u32>& bucket,
+                   const u64*& keys_out, u64& nkeys, const u32*& bk_out, const pos_t*& apos_out, u64& napos_out) {
+        u32 ni, nch;
+        u64 na;
+        ichunk* ch = runs_to_chunks(bm, E.g_ast, E.g_aen, E.g_ark, E.chunk_buf2, ni, na, nch);
+        nkeys = 0;
+        keys_out = nullptr;
+        apos_out = nullptr;
+        napos_out = 0;
+        if (!na) return 0;
+        u32* akey32 = k32.get(5 * na);
+        pos_t* apos = kpos.get(na);
+        apos_out = apos;
+        napos_out = na;
+        k_slots<<<cdiv(nch, SL_CH), SL_T, 0, st>>>(C.T, C.G, ch, nch, akey32, nullptr, apos);
+        u64* ak = ka.get(5 * na);
+        u64* ak2 = kb.get(5 * na);
+        k_pack_added<<<cdiv(5 * na, 256), 256, 0, st>>>(akey32, apos, 5 * na, ak);
+        size_t tb = 0;
+        LZ_HIP(rocprim::radix_sort_keys(nullptr, tb, ak, ak2, (size_t)(5 * na), 0u, 63u, st));
+        u8* t = E.scan_tmp.get(tb);
+        LZ_HIP(rocprim::radix_sort_keys(t, tb, ak, ak2, (size_t)(5 * na), 0u, 63u, st));
+        keys_out = ak2;
+        nkeys = 5 * na;
+        build_buckets(E, nslots, key_u64{ak2}, 5 * na, bucket);
+        bk_out = bucket.p;
+        return na;
+    }
+    void rebuild_main() {
+        bmA_zero = false;
+        k_bm_andnot<<<gw, 256, 0, st>>>(bmI, bmIb, nw, bmA);
+        na_main = build_list(bmA, E.add_keys32, E.add_pos, E.add_keys, E.add_keys2, E.g_abeg, W.akeys, W.nadd, W.abeg,
+                             W.apos, W.napos);
+        W.nadd2 = 0;
+        W.akeys2 = nullptr;
+    }
+    void rebuild_added(bool main_list) {
+        if (main_list) return rebuild_main();
+        k_bm_andnot<<<gw, 256, 0, st>>>(bmI, bmIb, nw, bmT);
+        if (!bmA_zero) k_bm_andnot<<<gw, 256, 0, st>>>(bmT, bmA, nw, bmT);
+        const u64 nx = build_list(bmT, E.g_x32, E.g_xpos, E.g_xk, E.g_xk2, E.g_abeg2, W.akeys2, W.nadd2, W.abeg2, W.apos2,
+                                  W.napos2);
+        if (nx * 4 > na_main + (1u << 16)) rebuild_main();
+    }
+    // rem + added for the current I; within_base: I is a subset of the base set (the first
+    // speculation, or a base rebuilt as I' u I_b), so no position is added and the main list
+    // (I - I_b, a full-length bitmap pass and a count) is empty without computing it
+    void set_state(bool within_base) {
+        W.bmI = bmI;
+        I_fresh = within_base;
+        if (nb)
+            k_rem_from_bm<<<cdiv(nb, 256), 256, 0, st>>>(W.ipos, nb, bmI, off, (u8*)W.rem, (pos_t*)W.iposr);
+        if (!within_base) return rebuild_added(true);
+        bmA_zero = true;
+        na_main = 0;
+        W.akeys = nullptr; W.nadd = 0; W.abeg = nullptr; W.apos = nullptr; W.napos = 0;
+        W.akeys2 = nullptr; W.nadd2 = 0;
+    }
+
+    // ---- one round: walks the segments that need it; returns their number
+    u32 walk_todo() {
+        LZ_HIP(hipMemsetAsync(d_cnt, 0, 4, st));
+        k_todo<<<cdiv(nseg, 256), 256, 0, st>>>(S, nseg, ids, d_cnt);
+        const u32 ntodo = rd1(d_cnt, st);
+        const u32* wids = ids;
+        if (ntodo >= (1u << 16)) {  // sort the walks by expected length: less divergence per wave
+            u32* wk = E.g_wk.get(2ull * ntodo);
+            u32* ids2 = E.g_ids2.get(ntodo);
+            k_walk_keys<<<cdiv(ntodo, 256), 256, 0, st>>>(S, ids, ntodo, wk);
+            size_t tb = 0;
+            LZ_HIP(rocprim::radix_sort_pairs_desc(nullptr, tb, wk, wk + ntodo, ids, ids2, (size_t)ntodo, 0u, 32u, st));
+            u8* t = E.scan_tmp.get(tb);
+            LZ_HIP(rocprim::radix_sort_pairs_desc(t, tb, wk, wk + ntodo, ids, ids2, (size_t)ntodo, 0u, 32u, st));
+            wids = ids2;
+        }
+        if (ntodo) {
+            k_walk<false><<<cdiv(ntodo, 64), 64, 0, st>>>(W, S, wids, ntodo, nullptr, nullptr);
+            LZ_HIP(hipGetLastError());
+            walked_total += ntodo;
+        }
+        C.lap(st, "walk");
+        return ntodo;
+    }
+    // links every segment to its successor (k_link); grows the table when full
+    void link() {
+        for (;;) {
+            k_link<<<cdiv(nseg, 256), 256, 0, st>>>(S, nseg);
+            u32 h2[2];
+            {
+                hread rb(st);
+                rb.add(h2, (const u32*)S.nseg, 2);
+                rb.sync();
+            }
+            if (!(h2[1] & 1)) { nseg = h2[0]; break; }
+            const u32 ncap = cap * 2;
+            E.g_sin.grow_keep(ncap, cap, st); E.g_sout.grow_keep(ncap, cap, st);
+            E.g_stash.grow_keep((u64)ncap * 2 * STASH_CAP, (u64)cap * 2 * STASH_CAP, st);
+            E.g_valid.grow_keep(ncap, cap, st); E.g_succ.grow_keep(ncap, cap, st);
+            E.g_ids.get(ncap);
+            ids = E.g_ids.p;
+            cap = ncap;
+            bind_tab();
+            const u32 fix[2] = {cap < h2[0] ? cap : h2[0], h2[1] & ~1u};
+            LZ_HIP(hipMemcpyAsync(S.nseg, fix, 8, hipMemcpyHostToDevice, st));
+            LZ_HIP(hipStreamSynchronize(st));
+        }
+    }
+    // pointer doubling along succ from every segment -> the status of the chain from the entry (cs)
+    void double_pointers() {
+        u32* D0 = E.g_dist[0].get(nseg);
+        u32* D1 = E.g_dist[1].get(nseg);
+        k_jump0<<<cdiv(nseg, 256), 256, 0, st>>>(S, nseg, E.jump[0].get(nseg), D0);
+        u32 nlv = 1;
+        while ((1ull << (nlv - 1)) < nseg) {
+            if (nlv + 1 >= (u32)MAX_LV) throw error(-6, "greedy: too many jump levels");
+            if ((1ull << nlv) < nseg) {  // two levels in one launch
+                k_jumpk2<<<cdiv(nseg, 256), 256, 0, st>>>(E.jump[nlv - 1].p, D0, nseg, E.jump[nlv].get(nseg),
+                                                          E.jump[nlv + 1].get(nseg), D1);
+                nlv += 2;
+            } else {
+                k_jumpk<<<cdiv(nseg, 256), 256, 0, st>>>(E.jump[nlv - 1].p, D0, nseg, E.jump[nlv].get(nseg), D1);
+                nlv++;
+            }
+            std::swap(D0, D1);
+        }
+        JL.nlv = nlv;
+        for (u32 l = 0; l < nlv; l++) JL.J[l] = E.jump[l].p;
+        k_chain_status<<<1, 1, 0, st>>>(S, E.jump[nlv - 1].p, D0, c0, d_cs);
+        {
+            hread rb(st);
+            rb.add(&cs, (const chain_status*)d_cs);
+            rb.sync();
+        }
+        C.lap(st, "link");
+    }
+    // ---- walk + link until the chain from the window entry is complete.  false: a walk
+    // overflowed or linking ran away (complete sequentially from the entry)
+    bool complete_chain() {
+        for (int round = 0;; round++) {
+            rounds_total++;
+            if (round > 100000) return false;
+            const u32 ntodo = walk_todo();
+            link();
+            double_pointers();
+            if (cs.err & 6) return false;  // 2: LPF-start query overflow, 4: walk guard
+            if (C.dbg)
+                std::fprintf(stderr,
+                             "[lz77sss-debug] greedy window=%d outer=%d round=%d segs=%u walked=%u chain=%u valid=%u "
+                             "flags=%u\n",
+                             nwin, outer, round, nseg, ntodo, cs.hops + 1, cs.valid, cs.flags);
+            if (cs.valid && ((cs.flags & 1) || cs.next >= bw)) return true;
+        }
+    }
+
+    // ---- the chain's nodes in order and their factor offsets
+    void expand_chain() {
+        nall = cs.hops + 1;
+        nchain = nall - (tail ? 1u : 0u);
+        chain = E.g_chain.get(nall + 1);
+        k_chain_expand<<<cdiv(nall, 256), 256, 0, st>>>(JL, nall, c0, chain);
+        u64* nf = E.seg_offs.get(nall + 2);
+        offs = E.g_offs.get(nall + 2);
+        chain_fact = 0;
+        if (nchain) {
+            k_chain_nfact<<<cdiv(nchain, 256), 256, 0, st>>>(S, chain, nchain, nf);
+            chain_fact = excl_scan(nf, offs, nchain, E.scan_tmp, st);
+        }
+    }
+    // ---- the tail (the last 64 positions, one thread with an exact local model) behind the chain's
+    // factors; sizes the factor buffer either way.  Its inserts stay in tail_ins_buf (tail_nins)
+    void walk_tail() {
+        tail_count = tail_nins = 0;
+        if (!tail) {
+            E.fact.get(2 * chain_fact + 2);
+            return;
+        }
+        seg_in tin;
+        seg_out prev{};
+        {
+            hread rb(st);
+            rb.add(&tin, (const seg_in*)(E.g_sin.p + cs.term));
+            u32 pg = 0;
+            if (nall >= 2) rb.add(&pg, (const u32*)(chain + nall - 2));
+            rb.sync();
+            if (nall >= 2) {
+                rb.add(&prev, (const seg_out*)(E.g_sout.p + pg));
+                rb.sync();
+            }
+        }
+        if (nall >= 2) {  // exact chain state entering the tail walk
+            tin.idxpos = prev.idxpos;
+            tin.zmask = prev.zmask;
+        } else {
+            tin.idxpos = entry_in.idxpos;
+            tin.zmask = entry_in.zmask;
+        }
+        if (C.dbg)
+            std::fprintf(stderr, "[lz77sss-debug] greedy tail entry: start=%llu p=%u idxpos=%llu zmask=%u lim=%llu nall=%u\n",
+                         (unsigned long long)tin.start, tin.p, (unsigned long long)tin.idxpos, tin.zmask,
+                         (unsigned long long)tin.lim, nall);
+        const u64 tail_bound = (u64)C.N - tin.start + 1;
+        pos_t* fo = E.fact.get(2 * (chain_fact + tail_bound) + 2);
+        u64* d_tc = (u64*)E.g_tailc.get(4 * sizeof(u64));
+        pos_t* d_tins = E.tail_ins_buf.get(16);
+        k_tail<<<1, 64, 0, st>>>(W, tin, fo, chain_fact, d_tc, d_tins);
+        LZ_HIP(hipGetLastError());
+        u64 hc[3] = {0, 0, 0};
+        pos_t tail_pairs[16];
+        {
+            hread rb(st);
+            rb.add(hc, (const u64*)d_tc, 3);
+            rb.add(tail_pairs, (const pos_t*)d_tins, 16);
+            rb.sync();
+        }
+        if (hc[2]) throw error(-6, "greedy tail: insert overflow or guard tripped");
+        tail_count = hc[0];
+        tail_nins = hc[1];
+        C.lap(st, "tail");
+    }
+    // ---- the insert set the chain actually produced (I', bmI2) vs the speculation (I): the number
+    // of changed positions (their bitmap in bmT when it is not 0)
+    u64 compare_inserts() {
+        const bool fast = I_fresh && !C.K.no_fast_check;
+        // a long gap is walked by one wave: with few chain nodes, the long ranges go to the
+        // whole grid instead
+        constexpr u32 LNG_CAP = 1024;
+        u32* lng = nchain ? (u32*)E.g_lng.get(2 + 4 * LNG_CAP) : nullptr;
+        E.fills({{bmI2, nw * 4, 0u}, {fast ? i_cnt : nullptr, 8, 0u}, {lng, 8, 0u}});
+        if (nchain) {
+            const u32 lng_cap = std::min(LNG_CAP, C.K.lng_cap);
+            k_chain_inserts<<<capped_grid((u64)nchain * 64, 256), 256, 0, st>>>(S, chain, nchain, hi_ins, off, bmI2, bmI,
+                                                                             fast ? i_cnt : nullptr, C.K.long_words, lng,
+                                                                             lng_cap);
+            k_chain_inserts_long<<<1024, 256, 0, st>>>(lng, lng_cap, bmI2, bmI, fast ? i_cnt : nullptr);
+        }
+        if (tail && tail_nins)
+            k_set_pairs<<<1, 64, 0, st>>>(E.tail_ins_buf.p, (u32)tail_nins, off, bmI2, bmI, fast ? i_cnt : nullptr);
+        bool same = false;
+        if (fast) {
+            // I' == I  <=>  no insert outside I  and  every position of I (all base ranks
+            // not removed: I lies within the base set) inserted
+            if (nb) k_subset_check<<<cdiv(nb, 256), 256, 0, st>>>(W.ipos, W.rem, nb, bmI2, off, i_cnt + 1);
+            u32 ic[2];
+            hread rb(st);
+            rb.add(ic, (const u32*)i_cnt, 2);
+            rb.sync();
+            same = ic[0] == 0 && ic[1] == 0;
+            if (C.dbg)
+                std::fprintf(stderr, "[lz77sss-debug] greedy fast check: inserts outside I=%u, waves with I positions "
+                             "not inserted=%u -> %s\n", ic[0], ic[1], same ? "equal" : "full check");
+        }
+        u64 ny = 0;
+        if (!same) {
+            k_bm_xor<<<gw, 256, 0, st>>>(bmI2, bmI, nw, bmT);
+            ny = bmb_scan(bm_bits{bmT, nullptr}, nw, E.g_bsum, E.g_bincl, E.scan_tmp, st) >> 32;
+        }
+        C.lap(st, "insert set");
+        return ny;
+    }
+    // LZ77SSS_DEBUG_JUMP: which phrases the converged chain rolled over (interior in I), by log2 length
+    void debug_jump_histogram() {
+        const u32 m = C.m;
+        std::vector<u32> hb(nw);
+        std::vector<pos_t> hp(3 * ((u64)m + 1));
+        LZ_HIP(hipStreamSynchronize(st));
+        LZ_HIP(hipMemcpy(hb.data(), bmI, nw * 4, hipMemcpyDeviceToHost));
+        LZ_HIP(hipMemcpy(hp.data(), C.P, hp.size() * sizeof(pos_t), hipMemcpyDeviceToHost));
+        u64 tot[2][40] = {}, jmp[2][40] = {}, jpos[2][40] = {};
+        pos_t prev_end = 0;
+        for (u32 k = 0; k < m; k++) {
+            const pos_t b0 = hp[3 * k], b1 = hp[3 * k + 1];
+            const int g = b0 > prev_end ? 1 : 0;
+            prev_end = b1;
+            if (b0 < a || b1 >= hi_ins || b1 - b0 < 4) continue;
+            int lg = 0;
+            while (((pos_t)2 << lg) <= b1 - b0) lg++;
+            const pos_t q = b0 + (b1 - b0) / 2 - off;
+            tot[g][lg]++;
+            if ((hb[q >> 5] >> (q & 31)) & 1) { jmp[g][lg]++; jpos[g][lg] += b1 - b0; }
+        }
+        for (int g = 0; g < 2; g++)
+            for (int lg = 0; lg < 40; lg++)
+                if (tot[g][lg])
+                    std::fprintf(stderr, "[lz77sss-debug] jump %s len 2^%d: phrases=%llu rolled=%llu pos=%llu\n",
+                                 g ? "after-gap" : "adjacent", lg, (unsigned long long)tot[g][lg],
+                                 (unsigned long long)jmp[g][lg], (unsigned long long)jpos[g][lg]);
+    }
+    // ---- every lookup of the chain was exact: emit the factors; the window exit and the carried
+    // table's update in one round trip
+    void emit() {
+        if (nchain) {
+            k_walk<true><<<cdiv(nchain, 64), 64, 0, st>>>(W, S, chain, nchain, offs, E.fact.p);
+            LZ_HIP(hipGetLastError());
+            C.lap(st, "write");
+        }
+        if (!last) {
+            seg_in* d_ex = (seg_in*)(d_sq + 16);
+            k_exit_state<<<1, 1, 0, st>>>(S, cs.term, d_ex);
+            hread rb(st);
+            rb.add(&exit_in, (const seg_in*)d_ex);
+            k_h_export<<<capped_grid((u64)nchain * 64, 256), 256, 0, st>>>(C.T, C.G, S, chain, nchain, C.Hs);
+            rb.sync();
+        }
+        wfact = chain_fact + tail_count;
+    }
+
+    // I' becomes I (the buffers trade places; the old I is the next round's I' scratch)
+    void swap_I() {
+        std::swap(E.g_bmI.p, E.g_bmI2.p), std::swap(E.g_bmI.cap, E.g_bmI2.cap);
+        bmI = E.g_bmI.p;
+        bmI2 = E.g_bmI2.p;
+    }
+    // ---- ny positions changed (bitmap bmT): the next speculation is I', applied in one of three ways
+    void apply_delta(u64 ny) {
+        // positions that joined (flag 1) or left (0) I
+        pos_t* d_y = E.dirty_in.get(ny + 1);
+        u8* d_j = (u8*)E.tmp_greedy2.get(2 * ny + 2);
+        k_bmb_write<<<bmb_blocks, BMB_T, 0, st>>>(bm_bits{bmT, nullptr}, nw, E.g_bincl.p, out_list{d_y, d_j, bmI2}, off);
+        const u64 outside = bmb_scan(bm_bits{bmI2, bmIb}, nw, E.g_bsum, E.g_bincl, E.scan_tmp, st) >> 32;
+        if (outside * 8 > nb) apply_rebuild_base(outside);
+        else if (ny > nseg) apply_full(ny, outside);
+        else apply_dirty(ny, outside, d_y, d_j);
+    }
+    // many positions outside the base set: rebuild it as I' u I_b, re-walk everything
+    void apply_rebuild_base(u64 outside) {
+        k_bm_or<<<gw, 256, 0, st>>>(bmI2, bmIb, nw, bmT);
+        swap_I();
+        build_base(bmT);
+        set_state(true);
+        k_invalidate_all<<<cdiv(nseg, 256), 256, 0, st>>>(S, nseg);
+        if (C.dbg) std::fprintf(stderr, "[lz77sss-debug] greedy rebuild: outside=%llu\n", (unsigned long long)outside);
+    }
+    // too many changes for dirty tracking to pay off: new state, re-walk everything
+    void apply_full(u64 ny, u64 outside) {
+        swap_I();
+        set_state(false);
+        k_invalidate_all<<<cdiv(nseg, 256), 256, 0, st>>>(S, nseg);
+        C.lap(st, "delta (full)");
+        if (C.dbg)
+            std::fprintf(stderr, "[lz77sss-debug] greedy delta (full): changed=%llu outside=%llu\n", (unsigned long long)ny,
+                         (unsigned long long)outside);
+    }
+    // dirty = changed positions + their same-slot successors before and after the update: only
+    // the segments holding one are walked again
+    void apply_dirty(u64 ny, u64 outside, pos_t* d_y, u8* d_j) {
+        pos_t* d_d = E.dirty_out.get(11 * ny + 1);
+        LZ_HIP(hipMemcpyAsync(d_d, d_y, ny * sizeof(pos_t), hipMemcpyDeviceToDevice, st));
+        k_dirty<<<cdiv(ny, 64), 64, 0, st>>>(W, d_y, ny, d_d + ny);
+        k_flip<<<cdiv(ny, 256), 256, 0, st>>>(W, d_y, d_j, ny, (u8*)W.rem, d_j + ny);
+        I_fresh = false;
+        swap_I();
+        LZ_HIP(hipMemsetAsync(d_cnt, 0, 4, st));
+        k_sum_u8<<<cdiv(ny, 256), 256, 0, st>>>(d_j + ny, ny, d_cnt);
+        W.bmI = bmI;
+        if (rd1(d_cnt, st)) rebuild_added(false);
+        k_dirty<<<cdiv(ny, 64), 64, 0, st>>>(W, d_y, ny, d_d + 6 * ny);
+        pos_t* d_ds = E.dirty_sorted.get(11 * ny + 1);
+        {
+            constexpr unsigned PB = 8 * sizeof(pos_t);
+            size_t tb = 0;
+            LZ_HIP(rocprim::radix_sort_keys(nullptr, tb, d_d, d_ds, (size_t)(11 * ny), 0u, PB, st));
+            u8* t = E.scan_tmp.get(tb);
+            LZ_HIP(rocprim::radix_sort_keys(t, tb, d_d, d_ds, (size_t)(11 * ny), 0u, PB, st));
+        }
+        k_stale<<<cdiv(nseg, 256), 256, 0, st>>>(S, nseg, d_ds, 11 * ny);
+        C.lap(st, "delta + dirty");
+        if (C.dbg)
+            std::fprintf(stderr, "[lz77sss-debug] greedy delta: changed=%llu outside=%llu\n", (unsigned long long)ny,
+                         (unsigned long long)outside);
+    }
+
+    // the window: speculate I, walk, compare, and iterate to the fixed point I' == I (or complete
+    // sequentially); leaves wfact factors in fact, exit_in, or redo
+    void run() {
+        const int max_outer = C.K.max_outer;
+        setup();
         if (max_outer == 0) {
             wfact = seq_complete(nullptr, 0, nullptr, nullptr, true);
         } else {
             build_base(bmIb);  // superset: gaps + short phrase interiors
             set_state(true);
-            bool restart_seq = false;  // a walk overflowed or linking ran away: complete from the entry
             for (;; outer++) {
-                for (int round = 0;; round++) {
-                    rounds_total++;
-                    if (round > 100000) { restart_seq = true; break; }
-                    LZ_HIP(hipMemsetAsync(d_cnt, 0, 4, st));
-                    k_todo<<<cdiv(nseg, 256), 256, 0, st>>>(S, nseg, ids, d_cnt);
-                    const u32 ntodo = rd1(d_cnt, st);
-                    const u32* wids = ids;
-                    if (ntodo >= (1u << 16)) {  // sort the walks by expected length: less divergence per wave
-                        u32* wk = g_wk.get(2ull * ntodo);
-                        u32* ids2 = g_ids2.get(ntodo);
-                        k_walk_keys<<<cdiv(ntodo, 256), 256, 0, st>>>(S, ids, ntodo, wk);
-                        size_t tb = 0;
-                        LZ_HIP(rocprim::radix_sort_pairs_desc(nullptr, tb, wk, wk + ntodo, ids, ids2, (size_t)ntodo, 0u,
-                                                              32u, st));
-                        u8* t = scan_tmp.get(tb);
-                        LZ_HIP(rocprim::radix_sort_pairs_desc(t, tb, wk, wk + ntodo, ids, ids2, (size_t)ntodo, 0u, 32u,
-                                                              st));
-                        wids = ids2;
-                    }
-                    if (ntodo) {
-                        k_walk<false><<<cdiv(ntodo, 64), 64, 0, st>>>(W, S, wids, ntodo, nullptr, nullptr);
-                        LZ_HIP(hipGetLastError());
-                        walked_total += ntodo;
-                    }
-                    lap("walk");
-                    for (;;) {  // link; grow the table when full
-                        k_link<<<cdiv(nseg, 256), 256, 0, st>>>(S, nseg);
-                        u32 h2[2];
-                        {
-                            hread rb(st);
-                            rb.add(h2, (const u32*)S.nseg, 2);
-                            rb.sync();
-                        }
-                        if (!(h2[1] & 1)) { nseg = h2[0]; break; }
-                        const u32 ncap = cap * 2;
-                        g_sin.grow_keep(ncap, cap, st); g_sout.grow_keep(ncap, cap, st);
-                        g_stash.grow_keep((u64)ncap * 2 * STASH_CAP, (u64)cap * 2 * STASH_CAP, st);
-                        g_valid.grow_keep(ncap, cap, st); g_succ.grow_keep(ncap, cap, st);
-                        g_ids.get(ncap);
-                        ids = g_ids.p;
-                        cap = ncap;
-                        bind_tab();
-                        const u32 fix[2] = {cap < h2[0] ? cap : h2[0], h2[1] & ~1u};
-                        LZ_HIP(hipMemcpyAsync(S.nseg, fix, 8, hipMemcpyHostToDevice, st));
-                        LZ_HIP(hipStreamSynchronize(st));
-                    }
-                    // pointer doubling along succ from every segment
-                    u32* D0 = g_dist[0].get(nseg);
-                    u32* D1 = g_dist[1].get(nseg);
-                    k_jump0<<<cdiv(nseg, 256), 256, 0, st>>>(S, nseg, jump[0].get(nseg), D0);
-                    u32 nlv = 1;
-                    while ((1ull << (nlv - 1)) < nseg) {
-                        if (nlv + 1 >= (u32)MAX_LV) throw error(-6, "greedy: too many jump levels");
-                        if ((1ull << nlv) < nseg) {  // two levels in one launch
-                            k_jumpk2<<<cdiv(nseg, 256), 256, 0, st>>>(jump[nlv - 1].p, D0, nseg, jump[nlv].get(nseg),
-                                                                      jump[nlv + 1].get(nseg), D1);
-                            nlv += 2;
-                        } else {
-                            k_jumpk<<<cdiv(nseg, 256), 256, 0, st>>>(jump[nlv - 1].p, D0, nseg, jump[nlv].get(nseg),
-                                                                     D1);
-                            nlv++;
-                        }
-                        std::swap(D0, D1);
-                    }
-                    JL.nlv = nlv;
-                    for (u32 l = 0; l < nlv; l++) JL.J[l] = jump[l].p;
-                    k_chain_status<<<1, 1, 0, st>>>(S, jump[nlv - 1].p, D0, c0, d_cs);
-                    {
-                        hread rb(st);
-                        rb.add(&cs, (const chain_status*)d_cs);
-                        rb.sync();
-                    }
-                    lap("link");
-                    if (cs.err & 6) { restart_seq = true; break; }  // 2: LPF-start query overflow, 4: walk guard
-                    if (dbg)
-                        std::fprintf(stderr,
-                                     "[lz77sss-debug] greedy window=%d outer=%d round=%d segs=%u walked=%u chain=%u valid=%u "
-                                     "flags=%u\n",
-                                     nwin, outer, round, nseg, ntodo, cs.hops + 1, cs.valid, cs.flags);
-                    if (cs.valid && ((cs.flags & 1) || cs.next >= bw)) break;
-                }
-                if (restart_seq) {
+                if (!complete_chain()) {
                     wfact = seq_complete(nullptr, 0, nullptr, nullptr, true);
                     break;
                 }
-                // ---- the chain, its factor offsets, the tail
-                const bool tail = cs.flags & 1;
+                tail = cs.flags & 1;
                 if (tail && !last) {
                     redo = true;
                     break;
                 }
-                const u32 nall = cs.hops + 1, nchain = nall - (tail ? 1u : 0u);
-                u32* chain = g_chain.get(nall + 1);
-                k_chain_expand<<<cdiv(nall, 256), 256, 0, st>>>(JL, nall, c0, chain);
-                u64* nf = seg_offs.get(nall + 2);
-                u64* offs = g_offs.get(nall + 2);
-                u64 chain_fact = 0;
-                if (nchain) {
-                    k_chain_nfact<<<cdiv(nchain, 256), 256, 0, st>>>(S, chain, nchain, nf);
-                    chain_fact = excl_scan(nf, offs, nchain, scan_tmp, st);
-                }
-                u64 tail_count = 0, tail_bound = 0;
-                pos_t tail_pairs[16];
-                u64 hc[3] = {0, 0, 0};
-                if (tail) {
-                    seg_in tin;
-                    seg_out prev{};
-                    {
-                        hread rb(st);
-                        rb.add(&tin, (const seg_in*)(g_sin.p + cs.term));
-                        u32 pg = 0;
-                        if (nall >= 2) rb.add(&pg, (const u32*)(chain + nall - 2));
-                        rb.sync();
-                        if (nall >= 2) {
-                            rb.add(&prev, (const seg_out*)(g_sout.p + pg));
-                            rb.sync();
-                        }
-                    }
-                    if (nall >= 2) {  // exact chain state entering the tail walk
-                        tin.idxpos = prev.idxpos;
-                        tin.zmask = prev.zmask;
-                    } else {
-                        tin.idxpos = entry_in.idxpos;
-                        tin.zmask = entry_in.zmask;
-                    }
-                    if (dbg)
-                        std::fprintf(stderr, "[lz77sss-debug] greedy tail entry: start=%llu p=%u idxpos=%llu zmask=%u lim=%llu nall=%u\n",
-                                     (unsigned long long)tin.start, tin.p, (unsigned long long)tin.idxpos, tin.zmask,
-                                     (unsigned long long)tin.lim, nall);
-                    tail_bound = (u64)N - tin.start + 1;
-                    pos_t* fo = fact.get(2 * (chain_fact + tail_bound) + 2);
-                    u64* d_tc = (u64*)g_tailc.get(4 * sizeof(u64));
-                    pos_t* d_tins = tail_ins_buf.get(16);
-                    k_tail<<<1, 64, 0, st>>>(W, tin, fo, chain_fact, d_tc, d_tins);
-                    LZ_HIP(hipGetLastError());
-                    {
-                        hread rb(st);
-                        rb.add(hc, (const u64*)d_tc, 3);
-                        rb.add(tail_pairs, (const pos_t*)d_tins, 16);
-                        rb.sync();
-                    }
-                    if (hc[2]) throw error(-6, "greedy tail: insert overflow or guard tripped");
-                    tail_count = hc[0];
-                    lap("tail");
-                } else {
-                    fact.get(2 * chain_fact + 2);
-                }
-                // ---- the insert set the chain actually produced vs the speculation
-                const bool fast = I_fresh && !std::getenv("LZ77SSS_NO_FAST_CHECK");
-                // a long gap is walked by one wave: with few chain nodes, the long ranges go to the
-                // whole grid instead
-                constexpr u32 LNG_CAP = 1024;
-                u32* lng = nchain ? (u32*)g_lng.get(2 + 4 * LNG_CAP) : nullptr;
-                fills({{bmI2, nw * 4, 0u}, {fast ? i_cnt : nullptr, 8, 0u}, {lng, 8, 0u}});
-                if (nchain) {
-                    // test knobs: a small list and a short "long" range make the overflow path run
-                    const u32 lng_cap = std::min(LNG_CAP, knob_lng_cap);
-                    const u32 long_words = knob_long_words;
-                    k_chain_inserts<<<capped_grid((u64)nchain * 64, 256), 256, 0, st>>>(S, chain, nchain, hi_ins, off, bmI2,
-                                                                                     bmI, fast ? i_cnt : nullptr, long_words,
-                                                                                     lng, lng_cap);
-                    k_chain_inserts_long<<<1024, 256, 0, st>>>(lng, lng_cap, bmI2, bmI, fast ? i_cnt : nullptr);
-                }
-                if (tail && hc[1]) {
-                    pos_t* d_tins = tail_ins_buf.p;
-                    k_set_pairs<<<1, 64, 0, st>>>(d_tins, (u32)hc[1], off, bmI2, bmI, fast ? i_cnt : nullptr);
-                }
-                bool same = false;
-                if (fast) {
-                    // I' == I  <=>  no insert outside I  and  every position of I (all base ranks
-                    // not removed: I lies within the base set) inserted
-                    if (nb) k_subset_check<<<cdiv(nb, 256), 256, 0, st>>>(W.ipos, W.rem, nb, bmI2, off, i_cnt + 1);
-                    u32 ic[2];
-                    hread rb(st);
-                    rb.add(ic, (const u32*)i_cnt, 2);
-                    rb.sync();
-                    same = ic[0] == 0 && ic[1] == 0;
-                    if (dbg)
-                        std::fprintf(stderr, "[lz77sss-debug] greedy fast check: inserts outside I=%u, waves with I positions "
-                                     "not inserted=%u -> %s\n", ic[0], ic[1], same ? "equal" : "full check");
-                }
-                u64 ny = 0;
-                if (!same) {
-                    k_bm_xor<<<gw, 256, 0, st>>>(bmI2, bmI, nw, bmT);
-                    ny = bmb_scan(bm_bits{bmT, nullptr}, nw, g_bsum, g_bincl, scan_tmp, st) >> 32;
-                }
-                lap("insert set");
-                if (ny == 0 && dbg && std::getenv("LZ77SSS_DEBUG_JUMP")) {
-                    // which phrases the converged chain rolled over (interior in I), by log2 length
-                    std::vector<u32> hb(nw);
-                    std::vector<pos_t> hp(3 * ((u64)m + 1));
-                    LZ_HIP(hipStreamSynchronize(st));
-                    LZ_HIP(hipMemcpy(hb.data(), bmI, nw * 4, hipMemcpyDeviceToHost));
-                    LZ_HIP(hipMemcpy(hp.data(), P, hp.size() * sizeof(pos_t), hipMemcpyDeviceToHost));
-                    u64 tot[2][40] = {}, jmp[2][40] = {}, jpos[2][40] = {};
-                    pos_t prev_end = 0;
-                    for (u32 k = 0; k < m; k++) {
-                        const pos_t b0 = hp[3 * k], b1 = hp[3 * k + 1];
-                        const int g = b0 > prev_end ? 1 : 0;
-                        prev_end = b1;
-                        if (b0 < a || b1 >= hi_ins || b1 - b0 < 4) continue;
-                        int lg = 0;
-                        while (((pos_t)2 << lg) <= b1 - b0) lg++;
-                        const pos_t q = b0 + (b1 - b0) / 2 - off;
-                        tot[g][lg]++;
-                        if ((hb[q >> 5] >> (q & 31)) & 1) { jmp[g][lg]++; jpos[g][lg] += b1 - b0; }
-                    }
-                    for (int g = 0; g < 2; g++)
-                        for (int lg = 0; lg < 40; lg++)
-                            if (tot[g][lg])
-                                std::fprintf(stderr, "[lz77sss-debug] jump %s len 2^%d: phrases=%llu rolled=%llu pos=%llu\n",
-                                             g ? "after-gap" : "adjacent", lg, (unsigned long long)tot[g][lg],
-                                             (unsigned long long)jmp[g][lg], (unsigned long long)jpos[g][lg]);
-                }
+                expand_chain();
+                walk_tail();
+                const u64 ny = compare_inserts();
+                if (ny == 0 && C.dbg && C.K.debug_jump) debug_jump_histogram();
                 if (ny == 0) {
-                    // every lookup of the chain was exact: emit the factors
-                    if (nchain) {
-                        k_walk<true><<<cdiv(nchain, 64), 64, 0, st>>>(W, S, chain, nchain, offs, fact.p);
-                        LZ_HIP(hipGetLastError());
-                        lap("write");
-                    }
-                    if (!last) {
-                        seg_in* d_ex = (seg_in*)(d_sq + 16);
-                        k_exit_state<<<1, 1, 0, st>>>(S, cs.term, d_ex);
-                        hread rb(st);
-                        rb.add(&exit_in, (const seg_in*)d_ex);
-                        k_h_export<<<capped_grid((u64)nchain * 64, 256), 256, 0, st>>>(T, G, S, chain, nchain, Hs);
-                        rb.sync();
-                    }
-                    wfact = chain_fact + tail_count;
+                    emit();
                     break;
                 }
                 if (outer + 1 >= max_outer) {
@@ -3033,94 +3151,140 @@ u64 engine::factorize_greedy(const u8* T, u32 rk_seed, int log2_override, greedy
                     wfact = seq_complete(chain, nall, offs, bmI2, false);
                     break;
                 }
-                // positions that joined (flag 1) or left (0) I
-                pos_t* d_y = dirty_in.get(ny + 1);
-                u8* d_j = (u8*)tmp_greedy2.get(2 * ny + 2);
-                k_bmb_write<<<bmb_blocks, BMB_T, 0, st>>>(bm_bits{bmT, nullptr}, nw, g_bincl.p, out_list{d_y, d_j, bmI2},
-                                                          off);
-                // many positions outside the base set: rebuild it as I' u I_b, re-walk everything
-                const u64 outside = bmb_scan(bm_bits{bmI2, bmIb}, nw, g_bsum, g_bincl, scan_tmp, st) >> 32;
-                if (outside * 8 > nb) {
-                    k_bm_or<<<gw, 256, 0, st>>>(bmI2, bmIb, nw, bmT);
-                    std::swap(g_bmI.p, g_bmI2.p), std::swap(g_bmI.cap, g_bmI2.cap);
-                    bmI = g_bmI.p;
-                    bmI2 = g_bmI2.p;
-                    build_base(bmT);
-                    set_state(true);
-                    k_invalidate_all<<<cdiv(nseg, 256), 256, 0, st>>>(S, nseg);
-                    if (dbg) std::fprintf(stderr, "[lz77sss-debug] greedy rebuild: outside=%llu\n", (unsigned long long)outside);
-                    continue;
-                }
-                if (ny > nseg) {
-                    // too many changes for dirty tracking to pay off: new state, re-walk everything
-                    std::swap(g_bmI.p, g_bmI2.p), std::swap(g_bmI.cap, g_bmI2.cap);
-                    bmI = g_bmI.p;
-                    bmI2 = g_bmI2.p;
-                    set_state(false);
-                    k_invalidate_all<<<cdiv(nseg, 256), 256, 0, st>>>(S, nseg);
-                    lap("delta (full)");
-                    if (dbg)
-                        std::fprintf(stderr, "[lz77sss-debug] greedy delta (full): changed=%llu outside=%llu\n",
-                                     (unsigned long long)ny, (unsigned long long)outside);
-                    continue;
-                }
-                // dirty = changed positions + their same-slot successors before and after the update
-                pos_t* d_d = dirty_out.get(11 * ny + 1);
-                LZ_HIP(hipMemcpyAsync(d_d, d_y, ny * sizeof(pos_t), hipMemcpyDeviceToDevice, st));
-                k_dirty<<<cdiv(ny, 64), 64, 0, st>>>(W, d_y, ny, d_d + ny);
-                k_flip<<<cdiv(ny, 256), 256, 0, st>>>(W, d_y, d_j, ny, (u8*)W.rem, d_j + ny);
-                I_fresh = false;
-                std::swap(g_bmI.p, g_bmI2.p), std::swap(g_bmI.cap, g_bmI2.cap);
-                bmI = g_bmI.p;
-                bmI2 = g_bmI2.p;
-                LZ_HIP(hipMemsetAsync(d_cnt, 0, 4, st));
-                k_sum_u8<<<cdiv(ny, 256), 256, 0, st>>>(d_j + ny, ny, d_cnt);
-                W.bmI = bmI;
-                if (rd1(d_cnt, st)) rebuild_added(false);
-                k_dirty<<<cdiv(ny, 64), 64, 0, st>>>(W, d_y, ny, d_d + 6 * ny);
-                pos_t* d_ds = dirty_sorted.get(11 * ny + 1);
-                {
-                    constexpr unsigned PB = 8 * sizeof(pos_t);
-                    size_t tb = 0;
-                    LZ_HIP(rocprim::radix_sort_keys(nullptr, tb, d_d, d_ds, (size_t)(11 * ny), 0u, PB, st));
-                    u8* t = scan_tmp.get(tb);
-                    LZ_HIP(rocprim::radix_sort_keys(t, tb, d_d, d_ds, (size_t)(11 * ny), 0u, PB, st));
-                }
-                k_stale<<<cdiv(nseg, 256), 256, 0, st>>>(S, nseg, d_ds, 11 * ny);
-                lap("delta + dirty");
-                if (dbg)
-                    std::fprintf(stderr, "[lz77sss-debug] greedy delta: changed=%llu outside=%llu\n", (unsigned long long)ny,
-                                 (unsigned long long)outside);
+                apply_delta(ny);
             }
         }
         k_seg_at_clear<<<cdiv(nseg, 256), 256, 0, st>>>(S, nseg);
-        seg_at_clean = true;
-        if (redo) {
-            if (dbg) std::fprintf(stderr, "[lz77sss-debug] greedy window %d reaches the tail region: walked again as the last\n", nwin);
+        E.seg_at_clean = true;
+    }
+};
+
+// a lead-in of a speculative block: the carried table seeded from the gap positions before it
+static void seed_carried(engine& E, const greedy_call& C) {
+    const u32 m = C.m;
+    hipStream_t st = E.st;
+    u32* cnt = E.g_tmp1.get(m + 2);
+    u32* off = E.g_tmp2.get(m + 2);
+    k_seed_counts<<<cdiv(m + 1, 256), 256, 0, st>>>(C.P, m, C.blk->start, cnt);
+    const u32 nch = excl_scan(cnt, off, m + 1, E.scan_tmp, st);
+    if (nch) k_seed_slots<<<cdiv(5ull * nch, 256), 256, 0, st>>>(C.T, C.G, C.P, m, C.blk->start, off, nch, C.Hs);
+    k_seed_queries<<<cdiv(5ull * (m + 1), 256), 256, 0, st>>>(C.T, C.G, C.P, m, C.blk->start, C.Hs);
+    LZ_HIP(hipGetLastError());
+}
+
+u64 engine::factorize_greedy(const u8* T, u32 rk_seed, int log2_override, greedy_block* blk) {
+    greedy_call C{};
+    C.dbg = debug_enabled();
+    C.t_mark = now_ms();
+    C.T = T;
+    C.blk = blk;
+    const greedy_knobs& K = C.K;
+    const pos_t N = C.N = (pos_t)n;
+    const u32 m = C.m = num_phr;
+    C.P = lpf.get((u64)(m + 1) * 3);
+    const phrase_stats ps = greedy_phrase_stats(*this, C.P, log2_override, true);
+    const gap_params_h& gp = C.gp = ps.gp;
+    // bases: rk_prime::random64(257, 2^20-1) from mt19937_64(rk_seed) (rolling_hash.hpp:127-130)
+    std::array<u64, 5> bases;
+    {
+        std::mt19937_64 g(rk_seed);
+        for (int i = 0; i < 5; i++) bases[i] = std::uniform_int_distribution<u64>(257, (1ull << 20) - 1)(g);
+    }
+    u128* d_negpow = upload_negpow(*this, bases, gp);
+
+    stats.assign(28, 0);
+    stats[0] = s; stats[1] = has_runs; stats[2] = m; stats[3] = ps.len_lpf_phr; stats[4] = ps.num_gaps;
+    for (int x = 0; x < 5; x++) stats[5 + x] = gp.patt_lens[x];
+    stats[10] = gp.roll_threshold; stats[11] = gp.log2_size_h;
+
+    gap_cfg& G = C.G;
+    G.n = N;
+    G.nt = N > 64 ? N - 64 : 0;
+    for (int x = 0; x < 5; x++) { G.lens[x] = gp.patt_lens[x]; G.base[x] = bases[x]; }
+    G.thr = gp.roll_threshold;
+    G.mask = (u32)((1ull << gp.log2_size_h) - 1);
+    G.negpow = d_negpow;
+    for (int x = 0; x < 5; x++) C.zmask0 |= (G.lens[x] >= N) ? (1u << x) : 0u;  // reinit(0) at construction
+    const u64 nslots_all = C.nslots_all = (u64)G.mask + 1;
+    C.use_pred = K.pred >= 0 ? K.pred : ((u64)(N - ps.len_lpf_phr) < 4096ull * (u64)std::max<u64>(1, ps.num_gaps)) ? 1 : 0;
+
+    // ---- windows (DESIGN.md 4.5): the chain is walked window by window; a window gets the
+    // exact chain state at its start and the table of the last insert per slot before it
+    // (pos + 1, 0 = none), and hands both on.  Windows bound the gap-index entry ids
+    // (32-bit) and every position-indexed structure to the window's span.  One window
+    // covers the text unless its base set would not fit (or LZ77SSS_GREEDY_WINDOW asks).
+    const u64 est_base = (u64)(N - ps.len_lpf_phr) + 49ull * (m + 1);  // gap positions + queries + short phrases
+    u64 WS = N;
+    if (K.window) {
+        WS = K.window;
+    } else if (est_base * 5 >= (1ull << 31)) {
+        // windows of ~2^31 / 10 base positions (uniform gap density assumed; a window whose base
+        // set still overflows the ids fails loudly in build_base)
+        WS = std::max<u64>(1ull << 20, (u64)((double)N * ((double)(1ull << 31) / 10.0) / (double)est_base));
+    }
+    // a block of a sharded factorization: [blk->start, blk->end) from the given chain state
+    const pos_t target_end = blk ? blk->end : N;
+    if (blk && (blk->end > N || blk->start >= blk->end || (blk->end < N && (u64)blk->end + 4096 > (u64)G.nt)))
+        throw error(LZ77SSS_EINVAL, "greedy block: need start < end and end == n or end <= n - 4160");
+    const bool carry = WS < (u64)N || blk;
+    if (carry) {
+        if (blk && blk->carried && g_Hs.cap < nslots_all)
+            throw error(LZ77SSS_EINVAL, "greedy block: carried table not loaded (size it with carried_entries)");
+        C.Hs = g_Hs.get(nslots_all);
+        if (!(blk && blk->carried)) LZ_HIP(hipMemsetAsync(C.Hs, 0, nslots_all * sizeof(pos_t), st));
+    }
+    if (blk && !blk->carried && blk->seed && blk->start > 0) seed_carried(*this, C);
+    if (blk && spec_track && nslots_all > spec_m)
+        throw error(LZ77SSS_EINVAL, "speculative block: the carried table changed size since spec_begin");
+    seg_in entry{0, 0, 0, C.zmask0, N};
+    if (blk) {
+        entry.start = blk->start;
+        entry.idxpos = blk->idxpos;
+        entry.zmask = blk->zmask;
+    }
+    u64 total_fact = 0, walked_all = 0;
+    int outer_all = 0, rounds_all = 0, nwin = 0;
+    u32 nseg_last = 0, nseg0_all = 0;
+    C.Lv = view(T);
+    // a non-last window (or block) whose chain reaches the tail region (a gap factor
+    // longer than the >= 4096 positions left after the window end) is walked again as the
+    // last window: the tail model needs every insert in the tail region before its start
+    bool force_last = false;
+
+    for (;;) {
+        // the window [a, bw): non-last windows end below the tail region (nt) and leave >= 4096 positions
+        const pos_t a = entry.start;
+        pos_t bw = force_last ? N : target_end;
+        if (!force_last && WS < (u64)(target_end - a) && (u64)a + WS + 4096 <= (u64)G.nt) bw = (pos_t)(a + WS);
+        greedy_window win(*this, C, entry, bw, nwin);
+        win.run();
+        if (win.redo) {
+            if (C.dbg) std::fprintf(stderr, "[lz77sss-debug] greedy window %d reaches the tail region: walked again as the last\n", nwin);
             force_last = true;
             stats[19] = 0;
             stats[23]++;
             continue;
         }
-        outer_all += max_outer == 0 ? 0 : outer + 1;
-        rounds_all += rounds_total;
-        walked_all += walked_total;
-        nseg_last = nseg;
-        nseg0_all += nseg0;
+        outer_all += K.max_outer == 0 ? 0 : win.outer + 1;
+        rounds_all += win.rounds_total;
+        walked_all += win.walked_total;
+        nseg_last = win.nseg;
+        nseg0_all += win.nseg0;
         nwin++;
         // the window's factors: fact[0, wfact); appended to the stream when there are several windows
+        const u64 wfact = win.wfact;
         if (carry) {
             pos_t* acc = fact_acc.grow_keep(2 * (total_fact + wfact) + 2, 2 * total_fact, st);
             if (wfact)
                 LZ_HIP(hipMemcpyAsync(acc + 2 * total_fact, fact.p, 2 * wfact * sizeof(pos_t), hipMemcpyDeviceToDevice, st));
         }
         total_fact += wfact;
-        if (last) {
+        if (win.last) {
             entry.start = N;
             break;
         }
-        entry = exit_in;
-        if (dbg)
+        entry = win.exit_in;
+        if (C.dbg)
             std::fprintf(stderr, "[lz77sss-debug] greedy window %d done: factors=%llu next=%llu\n", nwin - 1,
                          (unsigned long long)wfact, (unsigned long long)entry.start);
         if (entry.start >= target_end) break;

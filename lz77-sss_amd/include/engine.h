@@ -161,11 +161,9 @@ struct engine {
     dbuf<u8> tmp_greedy, chunk_buf, chunk_buf2, rem_buf;
     dbuf<u32> add_keys32;
     dbuf<pos_t> add_pos, dirty_in, dirty_out, dirty_sorted;
-    dbuf<u8> tmp_greedy2, tmp_greedy3;
+    dbuf<u8> tmp_greedy2;
     dbuf<u64> add_keys, add_keys2;
-    dbuf<seg_in> seg_in_buf;
-    dbuf<seg_out> seg_out_buf;
-    dbuf<u32> seg_ids, irank, ekeys, evals, ekeys2, evals2, occ_buf;
+    dbuf<u32> irank, ekeys, evals, ekeys2, evals2, occ_buf;
     dbuf<pos_t> ist, iend, ipos_buf, iposr_buf, tail_ins_buf;
     dbuf<u64> seg_offs, counters64;
     // device-resident greedy orchestration (csrc/greedy.hip)
